@@ -15,7 +15,11 @@ N GPUs (python -m torch.distributed.run ... bench.py --gpus N): every frame's ra
 renders its tiles of the K frames with a full model replica, and ONE RCCL all-gather of the K frames' [r,g,b,acc] tiles — captured in
 the same graph — assembles them on every rank; total work is fixed -> "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the --steps frames, writes the
+outputs of the last timed frame if --dump-outputs DIR is given, and prints the headline (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the frame statistics under config).  --full adds everything that takes runs of its own, as these extra objects:
+  replay_bit_exact — the frames of the last timed replay against separate eager renders of the same frames, bit for bit
+  stage_ms_per_step — HIP-event stage times of frame 0 rendered alone (a few eager frames after the timed region)
   roofline      — the dominant roofline-bound stage: the part MLPs (k_part_occ_all + k_winner_lists + k_part_rgb_all): algorithmic
                   FLOPs = 4.6 k x listed pairs + 17.5 k / 9.3 k x winning pairs (SURVEY.md §8d's 22.1 k / 14.0 k per pair split into
                   its two MLPs) / the stage's HIP-event time, vs the 157.3 TFLOP/s of fp32-in MFMA; measured HBM bytes and busy
@@ -32,7 +36,11 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with these extra
                   bounded sample of the same workload (N=1 only): one 4096-ray chunk + BASELINE configs[0]
   train_step, api_train_step — informational: configs[4]-shaped training iterations with the build's fused optimizer and with the
                   optimizer exactly as the reference's train_net.py builds it (N=1 only)
-The timed region is blocks of exactly --steps frames between fences, repeated until >= --min-time seconds.
+The timed region is exactly --steps frames between two fences (--min-time T: blocks of --steps frames, repeated until >= T seconds).
+
+--dump-outputs DIR: what the last timed step (frame) returned to its caller, as float32 .npy files: rgb_map.npy (rays, 3) and
+acc_map.npy (rays,) of the whole frame, and raw_sample.npy — a fixed, seeded sample of RAW_SAMPLE_ROWS rows of raw (ray-samples, 4)
+(occ is its last channel).  The same arguments give the same inputs from run to run.
 
 `--train [--train-config 377|lan] [--gpus N]` benches the training iteration instead (BASELINE configs[4] / configs[3]:
 fused forward + backward + dense Adam over the full-size model, data-parallel over N ranks), see main_train.
@@ -210,14 +218,36 @@ def winner_counts(out, stats):
 
 def frame_batches(res, cam_dist, K, dev):
     """K frames of a synthetic sequence: the same body, K poses / body orientations / latent codes (frame 0 = the frame of the round-1..3
-    bench lines).  -> (collated batches on the host, on the device)."""
-    cpu, gpu = [], []
-    for k in range(K):
+    bench lines).  -> (collated batches on the host, on the device).
+    The K scenes are built by a few host threads (their KD-tree queries release the GIL): ~1.4 s of host time each at 512 x 512."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    def one(k):
         bnp, _ = scene_mod.make_scene(res, res, seed=0, frame=(3 + 7 * k) % 100, cam_dist=cam_dist, pose_seed=k)
-        b = scene_mod.to_torch(bnp)
-        cpu.append(b)
-        gpu.append({kk: v.to(dev) for kk, v in b.items()})
+        return scene_mod.to_torch(bnp)
+    with ThreadPoolExecutor(max_workers=max(1, min(K, 8))) as ex:
+        cpu = list(ex.map(one, range(K)))
+    gpu = [{kk: v.to(dev) for kk, v in b.items()} for b in cpu]
     return cpu, gpu
+
+
+RAW_SAMPLE_ROWS = 1 << 18          # rows of raw in --dump-outputs (the whole tensor is n_rays x S x 16 B: ~0.5 GB at the bench shape)
+DUMP_SEED = 20240928
+
+
+def dump_outputs(path, full, local):
+    """--dump-outputs: the maps of the last timed frame (`full` = its (n, 4) [r, g, b, acc] rows in ray order) and a fixed, seeded
+    sample of its raw rows (`local` = what the frame's render call returned) as float32 .npy files under `path`."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    full = full.detach().float().cpu().numpy()
+    arrays = {'rgb_map': full[:, :3], 'acc_map': full[:, 3]}
+    if isinstance(local, dict) and local.get('raw') is not None:
+        raw = local['raw']
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(raw.shape[0], min(RAW_SAMPLE_ROWS, raw.shape[0]), replace=False))
+        arrays['raw_sample'] = raw[torch.from_numpy(rows).to(raw.device)].float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def frame_set(net, batches, S, rank, world, shard_of=0, want_raw=True, capture=True, capture_exchange=True, streams=False):
@@ -596,17 +626,22 @@ def main():
     ap.add_argument('--dense', action='store_true', help='stress variant: smpl_thresh=+inf (every sample active)')
     ap.add_argument('--no-raw', action='store_true', help='do not materialise raw/occ (N x 20 B)')
     ap.add_argument('--cam-dist', type=float, default=1.8, help='camera distance (m); 1.8 -> 97.6%% of the 512x512 pixels hit the body AABB')
-    ap.add_argument('--cpu-rays', type=int, default=4096, help='rays of the CPU-baseline chunk (BASELINE.md §3: one 4096-ray chunk)')
-    ap.add_argument('--min-time', type=float, default=1.0, help='repeat the timed K-step region until this many seconds are timed in total')
+    ap.add_argument('--cpu-rays', type=int, default=4096, help='--full: rays of the CPU-baseline chunk (BASELINE.md §3: one 4096-ray chunk)')
+    ap.add_argument('--min-time', type=float, default=0.0, help='repeat the timed --steps region until this many seconds are timed in total (0 = exactly --steps steps)')
     ap.add_argument('--full-rows', action='store_true', help='read the trainable 64-byte table rows instead of the eval-mode row-sum tables')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--train-iters', type=int, default=30, help='iterations of the informational training-step probe (0 = skip; N=1 only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--train-iters', type=int, default=30, help='--full: iterations of the informational training-step probe (0 = skip; N=1 only)')
     ap.add_argument('--no-graph', action='store_true', help='launch the ~25 kernels of a frame eagerly instead of replaying one captured hipGraph')
     ap.add_argument('--in-flight', type=int, default=10, help='frames of the sequence rendered side by side by one hipGraph replay (invr.frames); reduced to a divisor of --steps; 1 = strictly one frame at a time')
-    ap.add_argument('--no-variants', action='store_true', help='skip the S=64 / dense / full-row / shard-projection / API-frame variants of the default line')
+    ap.add_argument('--no-variants', action='store_true', help='--full: skip the S=64 / dense / full-row / shard-projection / API-frame variants')
     ap.add_argument('--shard-of', type=int, default=0, help='debug (1 GPU): render only rank 0\'s ray shard of a W-way split')
+    ap.add_argument('--full', action='store_true', help='also measure and check what takes runs of its own: replay bit-exactness, stage times, '
+                                                        'rooflines, variants, training probes, CPU baseline (see the module docstring)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step to DIR/<name>.npy (float32)')
     args = ap.parse_args()
     if args.train:
+        if args.dump_outputs:
+            ap.error('--dump-outputs writes the outputs of the render frames: not with --train')
         return main_train(args)
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -704,9 +739,9 @@ def main():
     for _ in range(max(1, -(-args.warmup // K))):
         fs.replay()
     fence()
-    # The timed region is EXACTLY K steps (frames) between two fences.  A frame takes ~2 ms, so one region is a few tens of
-    # milliseconds: the region is repeated (each repeat again exactly K steps between fences) until >= --min-time seconds
-    # have been timed, and the reported time per step is the mean over all repeats.
+    # The timed region is EXACTLY --steps steps (frames) between two fences.  With --min-time the region is repeated (each repeat
+    # again exactly --steps steps between fences) until >= --min-time seconds have been timed, and the reported time per step is the
+    # mean over all repeats.
     region = []
     while True:
         t0 = time.perf_counter()
@@ -728,44 +763,47 @@ def main():
         assert fs.full[k] is not None and fs.full[k].shape[0] == (rays_per_frame[k] if not args.shard_of else fs.full[k].shape[0])
         assert bool(torch.isfinite(fs.full[k]).all())
     frame_stats = [o['stats'].cpu().numpy().astype('int64') for o in fs.local]
-    # what the last timed replay produced, against separate renders of the same frames, bit for bit (every rank its own shards)
-    bit_exact, bit_detail = replay_bit_exact(fs, net, S, want_raw)
-    if world > 1:
-        flag = torch.tensor([1 if bit_exact else 0], device=dev)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        bit_exact = bool(int(flag.item()))
-    # the exchange alone (N > 1): the captured all-gather + index_selects replayed without the renders
-    exchange_ms = None
-    exchange_captured = bool(fs.exchange and fs.exchange_captured)
-    if world > 1 and fs.exchange and fs.exchange_captured:
-        try:
-            gx = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gx, capture_error_mode='thread_local'):
-                fs._exchange()
-            fence()
-            t0 = time.perf_counter()
-            for _ in range(50):
-                gx.replay()
-            fence()
-            exchange_ms = (time.perf_counter() - t0) / 50 * 1e3
-        except Exception as e:
-            sys.stderr.write('exchange-only timing failed (%s)\n' % e)
-    # per-stage HIP-event times: a few extra eager frames (frame 0) outside the timed region (event records are not
-    # replayable graph nodes)
-    net._ws = None
-    _abi.profile_enable(True)
-    _abi.profile_read()
-    for _ in range(3):
-        out = render()
-    torch.cuda.synchronize()
-    _abi.profile_enable(False)
-    stage_ms, n_prof = _abi.profile_read()
     if world > 1:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    stats = out['stats'].cpu().numpy().astype('int64')              # frame 0, this rank's shard (the eager profile frames)
-    assert stats[6] == 0, 'workspace overflow'
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fs.full[K - 1], fs.local[K - 1])      # the last timed step = frame K - 1 of the last replay
+    exchange_captured = bool(fs.exchange and fs.exchange_captured)
+    exchange_ms = None
+    if args.full:
+        # what the last timed replay produced, against separate renders of the same frames, bit for bit (every rank its own shards)
+        bit_exact, bit_detail = replay_bit_exact(fs, net, S, want_raw)
+        if world > 1:
+            flag = torch.tensor([1 if bit_exact else 0], device=dev)
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            bit_exact = bool(int(flag.item()))
+        # the exchange alone (N > 1): the captured all-gather + index_selects replayed without the renders
+        if world > 1 and fs.exchange and fs.exchange_captured:
+            try:
+                gx = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(gx, capture_error_mode='thread_local'):
+                    fs._exchange()
+                fence()
+                t0 = time.perf_counter()
+                for _ in range(50):
+                    gx.replay()
+                fence()
+                exchange_ms = (time.perf_counter() - t0) / 50 * 1e3
+            except Exception as e:
+                sys.stderr.write('exchange-only timing failed (%s)\n' % e)
+        # per-stage HIP-event times: a few extra eager frames (frame 0) outside the timed region (event records are not
+        # replayable graph nodes)
+        net._ws = None
+        _abi.profile_enable(True)
+        _abi.profile_read()
+        for _ in range(3):
+            out = render()
+        torch.cuda.synchronize()
+        _abi.profile_enable(False)
+        stage_ms, n_prof = _abi.profile_read()
+        stats = out['stats'].cpu().numpy().astype('int64')              # frame 0, this rank's shard (the eager profile frames)
+        assert stats[6] == 0, 'workspace overflow'
     stats_sum = sum(frame_stats)                                     # the K timed frames, this rank's shards
     if world > 1:
         st = torch.from_numpy(stats_sum).to(dev)
@@ -777,48 +815,8 @@ def main():
         total_samples = mean_rays * S                    # per step (frame): the K frames of the sequence differ by a few rays
         ms_per_step = dt / args.steps * 1e3
         value = total_samples * args.steps / dt          # dt = mean duration of one K-step region (= steps / K replays of K frames)
-        pairs_local = int(stats[1:6].sum())
-        winners = winner_counts(out, stats)              # rank 0's shard
-        n_rgb = [len(pn.rgb.linears) for pn in net.tpose_human.part_networks]
-        per = max(n_prof, 1)
-        enc_ms = sum(stage_ms['encode_%d' % p] for p in range(5)) / per
-        mlp_ms = sum(stage_ms['mlp_%d' % p] for p in range(5)) / per
-        knn_ms = stage_ms['knn'] / per
-        enc_bytes = pairs_local * (PAIR_TABLE_BYTES if args.full_rows else PAIR_TABLE_BYTES // 16)   # 16 levels x 8 corners x 64 B | 4 B
-        # part MLPs: occupancy MLP for every listed pair + colour MLP for the winning pair of every survivor (+ the far constants)
-        mlp_flops = OCC_FLOPS * pairs_local + sum(RGB_FLOPS[n_rgb[p]] * (winners[p] + 1) for p in range(5))
-        mlp_flops_ref = sum(int(stats[1 + p]) * (OCC_FLOPS + RGB_FLOPS[n_rgb[p]]) for p in range(5))      # what evaluating every pair costs
-        knn_flops = int(stats[0]) * 62000                                                                # brute-force 4-NN of the reference, SURVEY 8(d)
-        # per-kernel counters of the same command from the PMC passes (tools/prof_all.sh -> tools/prof_summary.py -> profiles/):
-        # HBM / Infinity-Cache bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE, the guide's gfx950 correction), busy and wait fractions
-        traffic, counters = {}, {}
         headline = world == 1 and not args.dense and args.table_log2 is None and args.res == 512 and S == 128 and not args.full_rows \
             and not args.shard_of
-        tf, cf = os.path.join(ROOT, 'profiles', 'hbm_traffic_per_launch.json'), os.path.join(ROOT, 'profiles', 'kernel_counters.json')
-        if headline and os.path.exists(tf):
-            traffic = json.load(open(tf))
-        if headline and os.path.exists(cf):
-            counters = json.load(open(cf))
-        meta = counters.pop('_meta', {}) if isinstance(counters, dict) else {}
-        traffic.pop('_meta', None)
-        # the profiler reports template instantiations by their full name: the eval frame's are <false> (arg-max merge)
-        for d in (traffic, counters):
-            for k in ('k_winner_lists', 'k_part_rgb_all'):
-                for suffix in ('<false>', '<0>'):          # (k_winner_lists is <0> since round 5's merge modes)
-                    if k not in d and k + suffix in d:
-                        d[k] = d.pop(k + suffix)
-        counters_stale = bool(traffic or counters) and meta.get('csrc_digest') != csrc_digest()
-        src = ('profiles/ (rocprofv3 --pmc passes of this command, tools/prof_all.sh; counters cannot be collected inside the timed run)'
-               + (' — STALE: measured on other kernel sources (digest %s, now %s)' % (meta.get('csrc_digest'), csrc_digest()) if counters_stale else '')
-               if traffic else None)
-        mlp_kernels = ('k_part_occ_all', 'k_winner_lists', 'k_part_rgb_all')
-        mlp_traffic = sum(traffic.get(k, 0) for k in mlp_kernels) if all(k in traffic for k in mlp_kernels) else None
-        # the byte model of SURVEY 8(d) / BASELINE.md §4 for the whole frame (a MODEL, not a bound: see path_roofline.note)
-        tab_b = PAIR_TABLE_BYTES if args.full_rows else PAIR_TABLE_BYTES // 16
-        path_bytes = (tab_b + 512 + 64) * pairs_local + 1920 * int(stats[0]) + (32 + (20 if want_raw else 0)) * int(ro.shape[0]) * S + 48 * int(ro.shape[0])
-        path_traffic = (sum(v for k, v in traffic.items() if k != 'k_row_sums') if traffic else None)      # (row sums: once per weight version)
-        tfl = lambda fl, ms: fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-        binding = lambda k: counters.get(k)
         line = {
             'metric': 'ray-samples/sec', 'value': value, 'unit': 'ray-samples/s', 'n_gpus': world,
             'survivors_per_sec': float(stats_all[0]) * args.steps / dt,      # co-headline: the samples that survive the cull and reach the networks
@@ -833,7 +831,6 @@ def main():
                 'survivors_per_sec': float(stats_all[0]) * args.steps / dt,
                 'pairs_per_part': [int(v) for v in stats_all[1:6]],
                 'pairs_per_active_sample': float(stats_all[1:6].sum()) / max(int(stats_all[0]), 1),
-                'colour_mlp_pairs_per_part_rank0': winners,
                 'parameters': int(n_params), 'raw_occ_materialised': want_raw, 'occ_is_raw_channel_3_view': True, 'hip_graph': use_graph, 'frames_in_flight': K,
                 'frames': '%d frames of a synthetic sequence (same body, %d poses / orientations / latent codes; frame 0 = the frame of the '
                           'round-1..3 lines) rendered side by side by ONE hipGraph replay (parallel branches, invr.frames.FrameSet); a step is '
@@ -850,89 +847,132 @@ def main():
                         'camera, survivors_per_sec the rate of the samples that reach the networks, mid_density the same sequence at '
                         'smpl_thresh 0.1' % (100.0 * float(stats_all[0]) / total_samples, args.cam_dist),
             },
-            # dominant roofline-bound stage: the tiny MLPs of all five parts on the fp32 matrix cores
-            'roofline': {
-                'kernel': 'part MLPs = k_part_occ_all (19-64-17 for every listed pair) + k_winner_lists + k_part_rgb_all (70-64(-64)-3 for the '
-                          'pair that wins each survivor\'s max-occupancy merge); occupancy MLP on v_mfma_f32_16x16x4_f32, the colour MLP\'s two '
-                          '64-wide layers on v_mfma_f32_16x16x32_bf16 as 3-way bf16 splits (6 products, fp32 accumulation: fp32 accuracy)', 'bound': 'mfma',
-                'achieved': tfl(mlp_flops, mlp_ms), 'peak': 157.3, 'unit': 'TFLOP/s', 'frac': tfl(mlp_flops, mlp_ms) / 157.3,
-                'traffic': mlp_traffic, 'traffic_source': src,
-                'algorithmic_flops_per_launch': int(mlp_flops), 'kernel_ms_per_launch': mlp_ms,
-                'flops_if_every_pair_ran_both_mlps': int(mlp_flops_ref),
-                'counters': {k: binding(k) for k in mlp_kernels} if counters else None,
-                'note': 'algorithmic = 4.6 kFLOP x listed pairs + 17.5 k (body, head) / 9.3 kFLOP (leg, arms) x winning pairs on rank 0 '
-                        '(SURVEY 8d\'s 22.1 k / 14.0 k split into its two MLPs; the reference evaluates both for every pair and discards the '
-                        'colour of all but the arg-max part, inb_part_network_multiassign.py:253-256); peak = the fp32-in MFMA peak (= fp32 vector peak '
-                        'on gfx950), kept as the yardstick for the ALGORITHMIC fp32 FLOPs although the colour layers now execute each algorithmic '
-                        'product as 6 bf16 products at 16x the fp32 MFMA rate (an fp32-accurate ceiling of 2.5 PFLOP/s / 6 = 417 TFLOP/s for those '
-                        'layers); time = HIP events on the launch stream around the three launches of the stage',
-            },
-            'roofline_other': [
-                {'kernel': 'k_knn_pairs (largest single kernel; exact per-part 4-NN)', 'bound': 'valu-issue (no HBM / MFMA roofline applies)',
-                 'achieved': tfl(knn_flops, knn_ms), 'peak': 157.3, 'unit': 'TFLOP/s (brute-force-equivalent)',
-                 'frac': None, 'traffic': traffic.get('k_knn_pairs'), 'kernel_ms_per_launch': knn_ms, 'counters': binding('k_knn_pairs'),
-                 'note': 'achieved = brute-force-EQUIVALENT rate: the search the reference runs costs 6890 vertices x ~9 FLOP = 62 kFLOP per '
-                         'survivor (SURVEY 8d); the cluster-pruned exact search executes roughly a tenth of it, so the figure can exceed the '
-                         'vector peak and no fraction is quoted; the binding resource is VALU issue (counters.valu_busy)'},
-                {'kernel': 'k_part_encode_rs_xcd (hash-grid gathers through the eval-mode row-sum tables)' if not args.full_rows
-                           else 'k_part_encode (64-byte table rows)',
-                 'bound': 'valu-issue + L2-miss latency (tables are L2 / Infinity-Cache resident)' if not args.full_rows else 'hbm',
-                 'measured_bytes_per_launch': traffic.get('k_part_encode_rs_xcd') if not args.full_rows else None,
-                 'measured_GBps': (traffic['k_part_encode_rs_xcd'] / (enc_ms * 1e-3) / 1e9) if (not args.full_rows and enc_ms > 0 and 'k_part_encode_rs_xcd' in traffic) else None,
-                 'kernel_ms_per_launch': enc_ms, 'counters': binding('k_part_encode_rs_xcd') if not args.full_rows else None,
-                 'nominal_model': {'bytes_per_launch': int(enc_bytes), 'GBps': enc_bytes / (enc_ms * 1e-3) / 1e9 if enc_ms > 0 else 0.0,
-                                   'frac_of_hbm_peak': (enc_bytes / (enc_ms * 1e-3) / HBM_PEAK) if enc_ms > 0 else 0.0,
-                                   'note': 'SECONDARY figure: SURVEY 8d\'s per-pair bytes (16 levels x 8 corners x %d B) x pairs — gathers that hit '
-                                           'L1 / L2 are counted, so this is not HBM traffic and can exceed 1 (64-byte rows: 1.96 in round 1)'
-                                           % (64 if args.full_rows else 4)}},
-            ],
-            'path_roofline': {
-                'bound': 'issue (VALU / MFMA) — no kernel of the frame is HBM-bound',
-                'measured_bytes_per_step': path_traffic, 'measured_GBps': (path_traffic / (ms_per_step * 1e-3) / 1e9) if path_traffic else None,
-                'measured_frac_of_hbm_peak': (path_traffic / (ms_per_step * 1e-3) / HBM_PEAK) if path_traffic else None,
-                'peak': HBM_PEAK / 1e9, 'unit': 'GB/s', 'traffic_source': src,
-                'nominal_model': {
-                    'bytes_per_step': int(path_bytes), 'GBps': path_bytes / (ms_per_step * 1e-3) / 1e9, 'frac_of_hbm_peak': path_bytes / (ms_per_step * 1e-3) / HBM_PEAK,
-                    'formula': '(%d + 512 + 64) B x evaluated pairs + 1920 B x survivors + (32%s) B x ray-samples + 48 B x rays (SURVEY 8d, rank 0 shard)'
-                               % (tab_b, ' + 20' if want_raw else ''),
-                    'note': 'SECONDARY figure, not a bound: the byte model counts every gather as memory traffic; the measured HBM / Infinity-Cache '
-                            'bytes are about a third of it (rows are reused from L1 / L2), and with the 64-byte rows the model prices the encoder '
-                            'above the HBM peak'},
-                'note': 'the frame is issue-bound: KNN = VALU, part MLPs = MFMA + transcendental issue, encoder = VALU index math + L2-miss '
-                        'latency; see roofline / roofline_other counters'},
-            'replay_bit_exact': bit_exact, 'replay_check': bit_detail,
-            'counters_stale': counters_stale, 'csrc_digest': csrc_digest(),
-            'stage_ms_per_step': {k: v / per for k, v in stage_ms.items()},
-            'stage_note': 'HIP-event stage times of frame 0 rendered ALONE (eager launches after the timed region); with %d frames in flight '
-                          'the stages of different frames overlap, so their sum exceeds ms_per_step' % K,
+            'cpu_baseline': None,
         }
-        if world == 1 and not args.no_variants and headline:
-            try:
-                del fs
-                out = None                   # (the eager profile frame holds a full-capacity workspace: 37.6 GB)
-                net._ws = None
-                torch.cuda.empty_cache()
-                line.update(variant_lines(net, cfg, batches, dev, S, K))
-            except Exception as e:          # informational: never lose the bench line over a variant
-                line['variants_error'] = repr(e)
-        if world == 1 and args.train_iters > 0 and not args.shard_of:
-            try:
-                line['train_step'] = train_probe(net, dev, S, args.train_iters)
-            except Exception as e:          # informational only: never lose the bench line over it
-                line['train_step'] = {'error': repr(e)}
-            try:
-                torch.cuda.empty_cache()
-                line['api_train_step'] = train_probe(net, dev, S, args.train_iters, fused=False)
-                line['api_train_step']['note'] = ('NetworkWrapper + the reference\'s own optimizer construction (torch.optim.Adam, 186 one-tensor '
-                                                  'groups) + its step form, nothing else changed: the drop-in training call.  The optimizer object is bound to the fused step at its first '
-                                                  'step() (invr.optim.adopt_on_first_step, installed by NetworkWrapper: shared param_groups / state, gradient arena); '
-                                                  'INVR_NO_OPTIM_HOOK=1 leaves torch\'s own Adam (9.3 ms in round 4).  train_step = the same with driver.make_optimizer (FusedAdam)')
-            except Exception as e:
-                line['api_train_step'] = {'error': repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
-            line['cpu_baseline'] = cpu_baseline(net, cfg, batch_cpu, min(args.cpu_rays, n_rays), S)
-        else:
-            line['cpu_baseline'] = None
+        if args.full:
+            pairs_local = int(stats[1:6].sum())
+            winners = winner_counts(out, stats)              # rank 0's shard
+            n_rgb = [len(pn.rgb.linears) for pn in net.tpose_human.part_networks]
+            per = max(n_prof, 1)
+            enc_ms = sum(stage_ms['encode_%d' % p] for p in range(5)) / per
+            mlp_ms = sum(stage_ms['mlp_%d' % p] for p in range(5)) / per
+            knn_ms = stage_ms['knn'] / per
+            enc_bytes = pairs_local * (PAIR_TABLE_BYTES if args.full_rows else PAIR_TABLE_BYTES // 16)   # 16 levels x 8 corners x 64 B | 4 B
+            # part MLPs: occupancy MLP for every listed pair + colour MLP for the winning pair of every survivor (+ the far constants)
+            mlp_flops = OCC_FLOPS * pairs_local + sum(RGB_FLOPS[n_rgb[p]] * (winners[p] + 1) for p in range(5))
+            mlp_flops_ref = sum(int(stats[1 + p]) * (OCC_FLOPS + RGB_FLOPS[n_rgb[p]]) for p in range(5))      # what evaluating every pair costs
+            knn_flops = int(stats[0]) * 62000                                                                # brute-force 4-NN of the reference, SURVEY 8(d)
+            # per-kernel counters of the same command from the PMC passes (tools/prof_all.sh -> tools/prof_summary.py -> profiles/):
+            # HBM / Infinity-Cache bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE, the guide's gfx950 correction), busy and wait fractions
+            traffic, counters = {}, {}
+            tf, cf = os.path.join(ROOT, 'profiles', 'hbm_traffic_per_launch.json'), os.path.join(ROOT, 'profiles', 'kernel_counters.json')
+            if headline and os.path.exists(tf):
+                traffic = json.load(open(tf))
+            if headline and os.path.exists(cf):
+                counters = json.load(open(cf))
+            meta = counters.pop('_meta', {}) if isinstance(counters, dict) else {}
+            traffic.pop('_meta', None)
+            # the profiler reports template instantiations by their full name: the eval frame's are <false> (arg-max merge)
+            for d in (traffic, counters):
+                for k in ('k_winner_lists', 'k_part_rgb_all'):
+                    for suffix in ('<false>', '<0>'):          # (k_winner_lists is <0> since round 5's merge modes)
+                        if k not in d and k + suffix in d:
+                            d[k] = d.pop(k + suffix)
+            counters_stale = bool(traffic or counters) and meta.get('csrc_digest') != csrc_digest()
+            src = ('profiles/ (rocprofv3 --pmc passes of this command, tools/prof_all.sh; counters cannot be collected inside the timed run)'
+                   + (' — STALE: measured on other kernel sources (digest %s, now %s)' % (meta.get('csrc_digest'), csrc_digest()) if counters_stale else '')
+                   if traffic else None)
+            mlp_kernels = ('k_part_occ_all', 'k_winner_lists', 'k_part_rgb_all')
+            mlp_traffic = sum(traffic.get(k, 0) for k in mlp_kernels) if all(k in traffic for k in mlp_kernels) else None
+            # the byte model of SURVEY 8(d) / BASELINE.md §4 for the whole frame (a MODEL, not a bound: see path_roofline.note)
+            tab_b = PAIR_TABLE_BYTES if args.full_rows else PAIR_TABLE_BYTES // 16
+            path_bytes = (tab_b + 512 + 64) * pairs_local + 1920 * int(stats[0]) + (32 + (20 if want_raw else 0)) * int(ro.shape[0]) * S + 48 * int(ro.shape[0])
+            path_traffic = (sum(v for k, v in traffic.items() if k != 'k_row_sums') if traffic else None)      # (row sums: once per weight version)
+            tfl = lambda fl, ms: fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+            binding = lambda k: counters.get(k)
+            line['config']['colour_mlp_pairs_per_part_rank0'] = winners
+            line.update({
+                # dominant roofline-bound stage: the tiny MLPs of all five parts on the fp32 matrix cores
+                'roofline': {
+                    'kernel': 'part MLPs = k_part_occ_all (19-64-17 for every listed pair) + k_winner_lists + k_part_rgb_all (70-64(-64)-3 for the '
+                              'pair that wins each survivor\'s max-occupancy merge); occupancy MLP on v_mfma_f32_16x16x4_f32, the colour MLP\'s two '
+                              '64-wide layers on v_mfma_f32_16x16x32_bf16 as 3-way bf16 splits (6 products, fp32 accumulation: fp32 accuracy)', 'bound': 'mfma',
+                    'achieved': tfl(mlp_flops, mlp_ms), 'peak': 157.3, 'unit': 'TFLOP/s', 'frac': tfl(mlp_flops, mlp_ms) / 157.3,
+                    'traffic': mlp_traffic, 'traffic_source': src,
+                    'algorithmic_flops_per_launch': int(mlp_flops), 'kernel_ms_per_launch': mlp_ms,
+                    'flops_if_every_pair_ran_both_mlps': int(mlp_flops_ref),
+                    'counters': {k: binding(k) for k in mlp_kernels} if counters else None,
+                    'note': 'algorithmic = 4.6 kFLOP x listed pairs + 17.5 k (body, head) / 9.3 kFLOP (leg, arms) x winning pairs on rank 0 '
+                            '(SURVEY 8d\'s 22.1 k / 14.0 k split into its two MLPs; the reference evaluates both for every pair and discards the '
+                            'colour of all but the arg-max part, inb_part_network_multiassign.py:253-256); peak = the fp32-in MFMA peak (= fp32 vector peak '
+                            'on gfx950), kept as the yardstick for the ALGORITHMIC fp32 FLOPs although the colour layers now execute each algorithmic '
+                            'product as 6 bf16 products at 16x the fp32 MFMA rate (an fp32-accurate ceiling of 2.5 PFLOP/s / 6 = 417 TFLOP/s for those '
+                            'layers); time = HIP events on the launch stream around the three launches of the stage',
+                },
+                'roofline_other': [
+                    {'kernel': 'k_knn_pairs (largest single kernel; exact per-part 4-NN)', 'bound': 'valu-issue (no HBM / MFMA roofline applies)',
+                     'achieved': tfl(knn_flops, knn_ms), 'peak': 157.3, 'unit': 'TFLOP/s (brute-force-equivalent)',
+                     'frac': None, 'traffic': traffic.get('k_knn_pairs'), 'kernel_ms_per_launch': knn_ms, 'counters': binding('k_knn_pairs'),
+                     'note': 'achieved = brute-force-EQUIVALENT rate: the search the reference runs costs 6890 vertices x ~9 FLOP = 62 kFLOP per '
+                             'survivor (SURVEY 8d); the cluster-pruned exact search executes roughly a tenth of it, so the figure can exceed the '
+                             'vector peak and no fraction is quoted; the binding resource is VALU issue (counters.valu_busy)'},
+                    {'kernel': 'k_part_encode_rs_xcd (hash-grid gathers through the eval-mode row-sum tables)' if not args.full_rows
+                               else 'k_part_encode (64-byte table rows)',
+                     'bound': 'valu-issue + L2-miss latency (tables are L2 / Infinity-Cache resident)' if not args.full_rows else 'hbm',
+                     'measured_bytes_per_launch': traffic.get('k_part_encode_rs_xcd') if not args.full_rows else None,
+                     'measured_GBps': (traffic['k_part_encode_rs_xcd'] / (enc_ms * 1e-3) / 1e9) if (not args.full_rows and enc_ms > 0 and 'k_part_encode_rs_xcd' in traffic) else None,
+                     'kernel_ms_per_launch': enc_ms, 'counters': binding('k_part_encode_rs_xcd') if not args.full_rows else None,
+                     'nominal_model': {'bytes_per_launch': int(enc_bytes), 'GBps': enc_bytes / (enc_ms * 1e-3) / 1e9 if enc_ms > 0 else 0.0,
+                                       'frac_of_hbm_peak': (enc_bytes / (enc_ms * 1e-3) / HBM_PEAK) if enc_ms > 0 else 0.0,
+                                       'note': 'SECONDARY figure: SURVEY 8d\'s per-pair bytes (16 levels x 8 corners x %d B) x pairs — gathers that hit '
+                                               'L1 / L2 are counted, so this is not HBM traffic and can exceed 1 (64-byte rows: 1.96 in round 1)'
+                                               % (64 if args.full_rows else 4)}},
+                ],
+                'path_roofline': {
+                    'bound': 'issue (VALU / MFMA) — no kernel of the frame is HBM-bound',
+                    'measured_bytes_per_step': path_traffic, 'measured_GBps': (path_traffic / (ms_per_step * 1e-3) / 1e9) if path_traffic else None,
+                    'measured_frac_of_hbm_peak': (path_traffic / (ms_per_step * 1e-3) / HBM_PEAK) if path_traffic else None,
+                    'peak': HBM_PEAK / 1e9, 'unit': 'GB/s', 'traffic_source': src,
+                    'nominal_model': {
+                        'bytes_per_step': int(path_bytes), 'GBps': path_bytes / (ms_per_step * 1e-3) / 1e9, 'frac_of_hbm_peak': path_bytes / (ms_per_step * 1e-3) / HBM_PEAK,
+                        'formula': '(%d + 512 + 64) B x evaluated pairs + 1920 B x survivors + (32%s) B x ray-samples + 48 B x rays (SURVEY 8d, rank 0 shard)'
+                                   % (tab_b, ' + 20' if want_raw else ''),
+                        'note': 'SECONDARY figure, not a bound: the byte model counts every gather as memory traffic; the measured HBM / Infinity-Cache '
+                                'bytes are about a third of it (rows are reused from L1 / L2), and with the 64-byte rows the model prices the encoder '
+                                'above the HBM peak'},
+                    'note': 'the frame is issue-bound: KNN = VALU, part MLPs = MFMA + transcendental issue, encoder = VALU index math + L2-miss '
+                            'latency; see roofline / roofline_other counters'},
+                'replay_bit_exact': bit_exact, 'replay_check': bit_detail,
+                'counters_stale': counters_stale, 'csrc_digest': csrc_digest(),
+                'stage_ms_per_step': {k: v / per for k, v in stage_ms.items()},
+                'stage_note': 'HIP-event stage times of frame 0 rendered ALONE (eager launches after the timed region); with %d frames in flight '
+                              'the stages of different frames overlap, so their sum exceeds ms_per_step' % K,
+            })
+            if world == 1 and not args.no_variants and headline:
+                try:
+                    del fs
+                    out = None                   # (the eager profile frame holds a full-capacity workspace: 37.6 GB)
+                    net._ws = None
+                    torch.cuda.empty_cache()
+                    line.update(variant_lines(net, cfg, batches, dev, S, K))
+                except Exception as e:          # informational: never lose the bench line over a variant
+                    line['variants_error'] = repr(e)
+            if world == 1 and args.train_iters > 0 and not args.shard_of:
+                try:
+                    line['train_step'] = train_probe(net, dev, S, args.train_iters)
+                except Exception as e:          # informational only: never lose the bench line over it
+                    line['train_step'] = {'error': repr(e)}
+                try:
+                    torch.cuda.empty_cache()
+                    line['api_train_step'] = train_probe(net, dev, S, args.train_iters, fused=False)
+                    line['api_train_step']['note'] = ('NetworkWrapper + the reference\'s own optimizer construction (torch.optim.Adam, 186 one-tensor '
+                                                      'groups) + its step form, nothing else changed: the drop-in training call.  The optimizer object is bound to the fused step at its first '
+                                                      'step() (invr.optim.adopt_on_first_step, installed by NetworkWrapper: shared param_groups / state, gradient arena); '
+                                                      'INVR_NO_OPTIM_HOOK=1 leaves torch\'s own Adam (9.3 ms in round 4).  train_step = the same with driver.make_optimizer (FusedAdam)')
+                except Exception as e:
+                    line['api_train_step'] = {'error': repr(e)}
+            if world == 1 and not args.no_cpu_baseline:
+                line['cpu_baseline'] = cpu_baseline(net, cfg, batch_cpu, min(args.cpu_rays, n_rays), S)
         print(json.dumps(line))
     if world > 1:
         dist.barrier()

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; N=${1:-1}; O=$R/gpurun_out/ab_order.txt; mkdir -p $R/gpurun_out; : > $O
 for i in $(seq $N); do
   for M in 1 0; do
-    INVR_ORDER=$M python $R/bench.py --steps 20 --warmup 5 --train-iters 0 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
+    INVR_ORDER=$M python $R/bench.py --full --steps 20 --warmup 5 --train-iters 0 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('INVR_ORDER=$M %.4f ms' % d['ms_per_step'], {k: round(v,3) for k,v in d['stage_ms_per_step'].items() if v})" | tee -a $O
   done

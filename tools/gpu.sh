@@ -58,7 +58,7 @@ import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$L %.3f ms/iter  k_adam %.3f ms  %.0f GB/s' % (d['ms_per_step'], r['kernel_ms_per_launch'], r['achieved']))"
       else
-        INVR_LIB_PATH=$GRAFT_REPO_ROOT/$L timeout 300 python bench.py --steps 20 --warmup 5 --train-iters 0 --no-cpu-baseline --no-variants "$@" 2>/dev/null | python -c "
+        INVR_LIB_PATH=$PWD/$L timeout 300 python bench.py --full --steps 20 --warmup 5 --train-iters 0 --no-cpu-baseline --no-variants "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L %.4f ms' % d['ms_per_step'], {k: round(v,3) for k,v in d['stage_ms_per_step'].items() if v})"
       fi
@@ -67,7 +67,7 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L %.4f ms' % d[
     # abn [tag] n lib1 lib2 ...: alternating runs of any number of library builds on this box
     N=$1; shift
     for i in $(seq $N); do for L in "$@"; do
-      INVR_LIB_PATH=$GRAFT_REPO_ROOT/$L timeout 300 python bench.py --steps 20 --warmup 5 --train-iters 0 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
+      INVR_LIB_PATH=$PWD/$L timeout 300 python bench.py --full --steps 20 --warmup 5 --train-iters 0 --no-cpu-baseline --no-variants 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L %.4f ms' % d['ms_per_step'], d.get('replay_bit_exact'), {k: round(v,3) for k,v in d['stage_ms_per_step'].items() if v})"
     done; done 2>&1 | tee $OUT/ab.log ;;
@@ -75,6 +75,6 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L %.4f ms' % d[
     timeout 1700 python -m pytest tests -q -m gpu --durations=8 > $OUT/pytest.log 2>&1; tail -12 $OUT/pytest.log
     bash tools/prof_all.sh ${T}_prof > $OUT/prof_all.log 2>&1; tail -5 $OUT/prof_all.log
     cd $GRAFT_REPO_ROOT
-    timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 400 $OUT/bench_default.json ;;
+    timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 400 $OUT/bench_default.json ;;
   *) echo "unknown task $task"; exit 2 ;;
 esac

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; T=$1
 OUT=$R/gpurun_out/$T; mkdir -p $OUT
-B="python $R/bench.py --no-cpu-baseline --no-variants --no-graph --train-iters 0"
+B="python $R/bench.py --full --no-cpu-baseline --no-variants --no-graph --train-iters 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $B --steps 10 --warmup 3 > $OUT/trace.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- $B --steps 2 --warmup 1 > $OUT/fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/write -o write -- $B --steps 2 --warmup 1 > $OUT/write.log 2>&1
@@ -11,5 +11,5 @@ rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYC
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE --output-format csv -d $OUT/mfma -o mfma -- $B --steps 2 --warmup 1 > $OUT/mfma.log 2>&1
 find $OUT -name "*_agent_info.csv" -delete
 find $OUT/trace -name "*kernel_trace.csv" -delete
-timeout ${2:-60} python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+timeout ${2:-60} python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
 tail -c 300 $OUT/bench.json; du -sh $OUT

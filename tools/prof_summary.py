@@ -11,10 +11,10 @@ import sys
 
 R, dst, title = sys.argv[1], sys.argv[2], sys.argv[3]
 out = ['# ' + title + '\n']
-out.append('Commands (MI355X box, `bash tools/prof_all.sh <tag>`): `python bench.py --steps 20 --warmup 5` (default flags, hipGraph replay), then\n'
-           '`rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --no-cpu-baseline --no-graph --steps 10 --warmup 3`, then one\n'
+out.append('Commands (MI355X box, `bash tools/prof_all.sh <tag>`): `python bench.py --full --steps 20 --warmup 5` (hipGraph replay), then\n'
+           '`rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --no-cpu-baseline --no-graph --steps 10 --warmup 3`, then one\n'
            '`rocprofv3 --kernel-trace --pmc <group> --output-format csv` run per counter group (`--steps 2 --warmup 1`; eager launches).\n')
-out.append('## bench.py (default flags) JSON line\n```\n' + open(R + '/bench.json').read().strip() + '\n```\n')
+out.append('## bench.py --full JSON line\n```\n' + open(R + '/bench.json').read().strip() + '\n```\n')
 rows = list(csv.DictReader(open(R + '/trace/trace_kernel_stats.csv')))
 short = lambda n: n.replace('void ', '').split('(')[0][:80]
 out.append('## kernel-trace stats (16 renders = 3 warm-up + 10 timed + 3 stage-profile frames)\n| kernel | calls | total_ms | avg_us | min_us | max_us | pct |\n|---|---|---|---|---|---|---|')

@@ -1,7 +1,7 @@
 import sys, os, json, subprocess
 # run bench (no cpu baseline) and print stage times compactly; extra args are passed through
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # repo root (this file lives in tools/)
-out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline"] + sys.argv[1:], capture_output=True, text=True)
+out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline"] + sys.argv[1:], capture_output=True, text=True)
 try:
     d = json.loads(out.stdout.strip().splitlines()[-1])
     st = d['stage_ms_per_step']
