@@ -443,6 +443,15 @@ int invr_train_bwd(const InvrScene* scene, const InvrModel* model, int64_t n_ray
  * grid's tables (every feature of a row takes the row's scalar); overwrites.  g_dense may be NULL for a non-separate table. */
 int invr_expand_row_grad(const InvrGrid* grid, const float* row_grad, float* g_dense, float* g_hash, void* stream);
 
+/* The encoder backward of one 16-level sum / sum_over_features part grid in the form invr_train_bwd runs it (invr_grid_encode_bwd is
+ * the AoS form with full-size table gradients): SoA pair lists with `stride` floats between components — x_soa (3 rows), g_out_soa
+ * (19 rows: the gradient of [normalised xyz, 16 level sums]) —, the number of pairs read on the DEVICE (*count <= n_max <= stride;
+ * n_max only sizes the launch), and the compact row-scalar table gradient.  ACCUMULATES (atomic float adds) into row_grad
+ * (invr_grid_row_sums_len floats, invr_grid_row_sums order, caller-zeroed) and writes rows [0, *count) of g_x_soa (3 rows, gradient
+ * w.r.t. the un-normalised input; NULL to skip).  Nothing past *count is read or written. */
+int invr_part_encode_bwd_lists(const InvrGrid* grid, const float* x_soa, const float* g_out_soa, int64_t stride,
+                               int64_t n_max, const int32_t* count, float* row_grad, float* g_x_soa, void* stream);
+
 /* The training objective of NetworkWrapper.forward (lib/train/trainers/inb_trainer.py:40-98, 176-214 with the plain MSE image term,
  * use_lpips False) on the outputs of invr_train_fwd, one launch each way:
  *   loss = w_pair * pair + w_dist * mean(dist) + w_off * offset + mean((rgb_map - rgb_gt)^2)      (the wrapper's order of additions)

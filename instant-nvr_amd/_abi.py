@@ -93,7 +93,7 @@ EXPORTS = ['invr_last_error', 'invr_version', 'invr_sizeof', 'invr_workspace_byt
            'invr_rigid_transformation', 'invr_pack_parts', 'invr_grid_row_sums_len', 'invr_grid_row_sums', 'invr_adam_chunk_elems', 'invr_adam_step', 'invr_part_mlp_fwd', 'invr_part_mlp_bwd',
            'invr_knn_neighbors', 'invr_pose_points', 'invr_adam_advance', 'invr_train_workspace_bytes', 'invr_train_fwd',
            'invr_train_bwd', 'invr_expand_row_grad', 'invr_train_loss_fwd', 'invr_train_loss_bwd',
-           'invr_part_encode_workspace', 'invr_part_encode_fwd']
+           'invr_part_encode_workspace', 'invr_part_encode_fwd', 'invr_part_encode_bwd_lists']
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
 BWD_HEAD, BWD_DEFORMER, BWD_ALL = 1, 64, 127
 NUM_STAGES = 14
@@ -142,6 +142,8 @@ def lib():
         L.invr_train_bwd.restype = C.c_int
         L.invr_expand_row_grad.argtypes = [C.POINTER(InvrGrid), vp, vp, vp, vp]
         L.invr_expand_row_grad.restype = C.c_int
+        L.invr_part_encode_bwd_lists.argtypes = [C.POINTER(InvrGrid), vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
+        L.invr_part_encode_bwd_lists.restype = C.c_int
         L.invr_train_loss_fwd.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp, vp]
         L.invr_train_loss_bwd.argtypes = [vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp, vp, vp, vp]
         L.invr_train_loss_fwd.restype = L.invr_train_loss_bwd.restype = C.c_int

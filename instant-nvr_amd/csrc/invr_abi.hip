@@ -958,3 +958,13 @@ extern "C" int invr_expand_row_grad(const InvrGrid* grid, const float* row_grad,
     INVR_LAUNCH_CHECK();
     return 0;
 }
+
+extern "C" int invr_part_encode_bwd_lists(const InvrGrid* grid, const float* x_soa, const float* g_out_soa, int64_t stride,
+                                          int64_t n_max, const int32_t* count, float* row_grad, float* g_x_soa, void* stream) {
+    INVR_CHECK(grid && count && row_grad, "invr_part_encode_bwd_lists: null pointer");
+    INVR_CHECK(n_max >= 0 && n_max <= stride && n_max < (1ll << 31), "invr_part_encode_bwd_lists: 0 <= n_max <= stride required");
+    if (n_max == 0) return 0;
+    INVR_CHECK(x_soa && g_out_soa, "invr_part_encode_bwd_lists: null pointer");
+    if (check_grid(grid, "part grid")) return 1;
+    return launch_part_encode_bwd_lists(make_grid_dev(grid), x_soa, g_out_soa, g_x_soa, stride, n_max, count, row_grad, (hipStream_t)stream);
+}
