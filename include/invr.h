@@ -468,6 +468,43 @@ int invr_train_loss_bwd(const float* rgb_map, const float* rgb_gt, const float* 
 int invr_composite_bwd(const float* raw, const float* g_rgb_map, const float* g_acc_map, const float* g_weights,
                        int64_t n_rays, int32_t n_samples, float* g_raw, void* stream);
 
+/* ---- evaluation metrics (lib/evaluators/if_nerf.py) on the device ------------------------------------------------------------
+ * The per-frame image metrics of the reference's Evaluator without a host round trip: the frame's numbers land in a caller-owned
+ * DEVICE result block of INVR_EVAL_RESULT_BYTES bytes (8-byte aligned) — float64[3] at byte 0 (INVR_EVAL_F_*), int32[8] at byte
+ * 24 (INVR_EVAL_I_*) — which the caller reads whenever it likes (psnr = -10 ln(SSE / count) / ln 10 is the host's to form, :28-31).
+ * Sums are float64 and formed in a fixed order (no floating-point atomics): the same inputs give the same bits in every run.
+ * workspace >= invr_eval_workspace_bytes(H, W), 256-byte aligned, shared by the two calls of a frame on one stream. */
+#define INVR_EVAL_RESULT_BYTES 64
+#define INVR_EVAL_F_SSE 0         /* sum over the H x W x 3 image of (double(pred) - double(gt))^2 (:112, :137 times their divisors) */
+#define INVR_EVAL_F_SUM_GT 1      /* sum of the ground-truth image (the `rgb_gt.sum() == 0` skip rule, :134-135)                    */
+#define INVR_EVAL_F_SUM_S 2       /* sum of the SSIM map over every window and the three channels: ssim = SUM_S / (3 WINDOWS)      */
+#define INVR_EVAL_I_WINDOWS 0     /* 7x7 windows fully inside the image / the rectangle: (h - 6)(w - 6), 0 when a side is < 7      */
+#define INVR_EVAL_I_X 1           /* cv2.boundingRect(mask) (:68): x, y, w, h; all 0 for an empty mask                             */
+#define INVR_EVAL_I_Y 2
+#define INVR_EVAL_I_W 3
+#define INVR_EVAL_I_H 4
+#define INVR_EVAL_I_STATUS 5      /* non-zero: the mask has another number of set entries than the n rows passed                   */
+#define INVR_EVAL_I_NSET 6        /* set entries of the mask                                                                       */
+size_t invr_eval_workspace_bytes(int32_t H, int32_t W);
+
+/* Evaluator.evaluate / ssim_metric image assembly (:39-42, :85-89: img = zeros((H,W,3)); img[mask_at_box] = rgb) for the rendered
+ * and the ground-truth pixels at once, cv2.boundingRect(mask) (:68) and the 8-bit image cv2.imwrite stores (:58-65, :106-107:
+ * img[..., [2,1,0]] * 255 through saturate_cast<uchar>(double): round half to even, clamp).  pred, gt (n,3) float32; mask (H*W)
+ * bytes, non-zero = set, in row-major pixel order: the k-th set pixel receives row k.  Outputs: img_pred, img_gt (H,W,3) float32
+ * (every pixel written); u8_pred, u8_gt (H,W,3) uint8 in B,G,R order or NULL; the INVR_EVAL_I_* words of `result` except WINDOWS.
+ * A mask whose number of set entries is not n sets STATUS; rows past n are never read (those pixels stay zero). */
+int invr_image_assemble(const float* pred, const float* gt, const uint8_t* mask, int64_t n, int32_t H, int32_t W,
+                        float* img_pred, float* img_gt, uint8_t* u8_pred, uint8_t* u8_gt, void* result,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* The frame's sums for mse / psnr (:28-31, :112-115, :137-140) and skimage.metrics.structural_similarity(img_pred, img_gt,
+ * channel_axis=2) of scikit-image 0.19.3 on float64 images with its defaults (:72, :126: uniform 7x7 window, K1 0.01, K2 0.03,
+ * sample covariance, data_range 2; the mean over the windows fully inside the image and the three channels), all statistics in
+ * float64.  img_pred, img_gt (H,W,3) float32.  crop = 0: SSIM over the whole frame (cfg.test_full, :126); crop = 1: over the
+ * rectangle INVR_EVAL_I_X.. that invr_image_assemble left in `result` (:68-72).  Writes the INVR_EVAL_F_* values and WINDOWS. */
+int invr_image_metrics(const float* img_pred, const float* img_gt, int32_t H, int32_t W, int32_t crop, void* result,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,9 +93,11 @@ EXPORTS = ['invr_last_error', 'invr_version', 'invr_sizeof', 'invr_workspace_byt
            'invr_rigid_transformation', 'invr_pack_parts', 'invr_grid_row_sums_len', 'invr_grid_row_sums', 'invr_adam_chunk_elems', 'invr_adam_step', 'invr_part_mlp_fwd', 'invr_part_mlp_bwd',
            'invr_knn_neighbors', 'invr_pose_points', 'invr_adam_advance', 'invr_train_workspace_bytes', 'invr_train_fwd',
            'invr_train_bwd', 'invr_expand_row_grad', 'invr_train_loss_fwd', 'invr_train_loss_bwd',
-           'invr_part_encode_workspace', 'invr_part_encode_fwd', 'invr_part_encode_bwd_lists']
+           'invr_part_encode_workspace', 'invr_part_encode_fwd', 'invr_part_encode_bwd_lists',
+           'invr_eval_workspace_bytes', 'invr_image_assemble', 'invr_image_metrics']
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
 BWD_HEAD, BWD_DEFORMER, BWD_ALL = 1, 64, 127
+EVAL_RESULT_BYTES = 64   # include/invr.h INVR_EVAL_RESULT_BYTES: float64[3] (SSE, sum gt, sum S), int32[8] (windows, x, y, w, h, status, set, 0)
 NUM_STAGES = 14
 STAGE_NAMES = ['cull', 'knn', 'warp'] + ['encode_%d' % p for p in range(5)] + ['mlp_%d' % p for p in range(5)] + ['composite']
 
@@ -189,6 +191,11 @@ def lib():
         L.invr_field_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
         L.invr_field_fwd.argtypes = [C.POINTER(InvrScene), C.POINTER(InvrModel), vp, vp, C.c_int64, vp, vp, vp, vp, C.c_size_t, C.c_int64, vp]
         L.invr_field_fwd.restype = C.c_int
+        L.invr_eval_workspace_bytes.restype = C.c_size_t
+        L.invr_eval_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+        L.invr_image_assemble.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+        L.invr_image_metrics.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_size_t, vp]
+        L.invr_image_assemble.restype = L.invr_image_metrics.restype = C.c_int
         L.invr_profile_enable.argtypes = [C.c_int32]
         L.invr_profile_read.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         for n in ('invr_render_fwd', 'invr_grid_encode_fwd', 'invr_sample_volume', 'invr_knn_blend',

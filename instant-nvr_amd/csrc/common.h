@@ -404,3 +404,7 @@ int launch_rigid_transformation(const double* poses, const double* joints, const
 int launch_pack_parts(const float* ppts, const float* weights, const int64_t* parts, const float* tpose, int n_verts, int n_w,
                       int stride, float overlap, float* part_pts, float* part_pbw, int64_t* lengths2, float* bounds, hipStream_t st);
 int launch_composite(const float* raw, int64_t n_rays, int S, float eps, float* weights, float* rgb_map, float* acc_map, hipStream_t st);
+size_t eval_workspace_bytes(int H, int W);
+int launch_image_assemble(const float* pred, const float* gt, const uint8_t* mask, int64_t n, int H, int W, float* img_pred,
+                          float* img_gt, uint8_t* u8_pred, uint8_t* u8_gt, void* result, void* ws, hipStream_t st);
+int launch_image_metrics(const float* img_pred, const float* img_gt, int H, int W, int crop, void* result, void* ws, hipStream_t st);

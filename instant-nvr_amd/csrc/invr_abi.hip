@@ -658,6 +658,41 @@ extern "C" int invr_generate_rays(const double* k_inv, const double* R, const do
     return launch_generate_rays(k_inv, R, T, cam_o, bounds, H, W, ray_d, near, far, mask, (hipStream_t)stream);
 }
 
+// ---- evaluation metrics (k_metrics.hip) ---------------------------------------------------------------------------------------
+#define INVR_EVAL_MAX_SIDE 16384          // (the window count and the pixel ranks are int32)
+extern "C" size_t invr_eval_workspace_bytes(int32_t H, int32_t W) {
+    if (H < 0 || W < 0 || H > INVR_EVAL_MAX_SIDE || W > INVR_EVAL_MAX_SIDE) return 0;
+    return eval_workspace_bytes(H, W);
+}
+
+static int check_eval_common(const char* who, int32_t H, int32_t W, const void* result, const void* workspace, size_t workspace_bytes) {
+    INVR_CHECK(H >= 0 && W >= 0 && H <= INVR_EVAL_MAX_SIDE && W <= INVR_EVAL_MAX_SIDE, "%s: H, W must be in [0, %d] (got %d x %d)", who,
+               INVR_EVAL_MAX_SIDE, H, W);
+    INVR_CHECK(result && workspace, "%s: null result block / workspace", who);
+    INVR_CHECK(((uintptr_t)result & 7) == 0, "%s: the result block must be 8-byte aligned", who);
+    INVR_CHECK(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", who);
+    INVR_CHECK(workspace_bytes >= eval_workspace_bytes(H, W), "%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes,
+               eval_workspace_bytes(H, W));
+    return 0;
+}
+
+extern "C" int invr_image_assemble(const float* pred, const float* gt, const uint8_t* mask, int64_t n, int32_t H, int32_t W,
+                                   float* img_pred, float* img_gt, uint8_t* u8_pred, uint8_t* u8_gt, void* result,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (check_eval_common("invr_image_assemble", H, W, result, workspace, workspace_bytes)) return 1;
+    INVR_CHECK(n >= 0 && n <= (int64_t)H * W, "invr_image_assemble: n must be in [0, H*W] (got %lld)", (long long)n);
+    INVR_CHECK(n == 0 || (pred && gt), "invr_image_assemble: null value pointer");
+    INVR_CHECK((int64_t)H * W == 0 || (mask && img_pred && img_gt), "invr_image_assemble: null mask / image pointer");
+    return launch_image_assemble(pred, gt, mask, n, H, W, img_pred, img_gt, u8_pred, u8_gt, result, workspace, (hipStream_t)stream);
+}
+
+extern "C" int invr_image_metrics(const float* img_pred, const float* img_gt, int32_t H, int32_t W, int32_t crop, void* result,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    if (check_eval_common("invr_image_metrics", H, W, result, workspace, workspace_bytes)) return 1;
+    INVR_CHECK((int64_t)H * W == 0 || (img_pred && img_gt), "invr_image_metrics: null image pointer");
+    return launch_image_metrics(img_pred, img_gt, H, W, crop != 0, result, workspace, (hipStream_t)stream);
+}
+
 extern "C" int invr_rigid_transformation(const double* poses, const double* joints, const int32_t* parents, float* A, void* stream) {
     INVR_CHECK(poses && joints && parents && A, "invr_rigid_transformation: null pointer");
     return launch_rigid_transformation(poses, joints, parents, A, (hipStream_t)stream);

@@ -39,16 +39,80 @@ def _lanes_that_fit(want, device):
     return max(1, min(want, int(free * 0.5 // (6 << 30))))
 
 
-def run_evaluate(net, batches, device='cuda', in_flight=None, renderer=None, keep_maps=False):
+HOST_KEYS = ('H', 'W', 'frame_index', 'cam_ind', 'orig_H', 'orig_W')          # scalars the evaluator reads with .item(): they stay where they are
+
+
+def _run_evaluate_device(net, batches, device, in_flight, renderer, evaluator):
+    """run_evaluate(metrics='device'): the loop of run.py:61-90 with the outputs left on the device and the reference's per-frame metrics
+    (lib/evaluators/if_nerf.py: mse, psnr, SSIM) computed there by invr.evaluator.Evaluator.  Per frame there is no device-to-host copy
+    and no host wait other than joining that frame's own event; the values of all frames are read back once, after the loop.  The
+    batch's H / W / frame_index / cam_ind stay host tensors when they arrive as such (.item() on a device scalar is a synchronisation)."""
+    from collections import deque
+    from .evaluator import Evaluator
+    own = renderer is None
+    renderer = renderer or Renderer(net)
+    if evaluator is None:
+        evaluator = Evaluator(cfg={'test_full': True, 'fast_eval': True, 'dry_run': False, 'eval_part': '', 'result_dir': ''})
+    prev_in_flight, prev_to_cpu = renderer.in_flight, renderer.eval_to_cpu
+    renderer.in_flight, renderer.eval_to_cpu = in_flight, False
+    queue = deque()
+
+    def finish(ret, batch):
+        ret['rgb_map']                                # joins the frame (a host wait on that frame's event only)
+        evaluator.evaluate(ret, batch)
+
+    failed = True
+    try:
+        for batch in batches:
+            batch = {k: (v.to(device) if torch.is_tensor(v) and not (k in HOST_KEYS and not v.is_cuda) else v) for k, v in batch.items()}
+            with torch.no_grad():
+                ret = renderer.render(batch)
+            queue.append((ret, batch))
+            while len(queue) >= renderer.in_flight:
+                finish(*queue.popleft())
+        while queue:
+            finish(*queue.popleft())
+        evaluator.collect()                            # the one read-back
+        failed = False
+    finally:
+        renderer.in_flight, renderer.eval_to_cpu = prev_in_flight, prev_to_cpu
+        if hasattr(renderer, 'flush'):
+            try:
+                renderer.flush(release=own)            # lanes are released only for a renderer created here
+            except Exception:
+                if not failed:                         # (a failing flush must not mask the first exception)
+                    raise
+    out = {'psnr': [float(v) for v in evaluator.psnr], 'mse': [float(v) for v in evaluator.mse], 'ssim': [float(v) for v in evaluator.ssim]}
+    if evaluator.lpips:
+        out['lpips'] = [float(v) for v in evaluator.lpips]
+    evaluator.mse, evaluator.psnr, evaluator.ssim, evaluator.lpips = [], [], [], []
+    return out
+
+
+def run_evaluate(net, batches, device='cuda', in_flight=None, renderer=None, keep_maps=False, metrics='host', evaluator=None):
     """-> dict(psnr=[...], mse=[...]) over an iterable of collated batches (CPU or device tensors): the loop of run.py:61-90 with
     `in_flight` frames kept on the GPU — frame f is submitted (Renderer.render returns at once, Renderer.in_flight lanes) and the
     metrics of frame f - in_flight + 1 are computed while the younger frames render; the values are those of one frame at a time
     (same kernels, a workspace per lane).  in_flight = 1: strictly render -> metrics -> next batch, as the reference.
     in_flight = None: cfg.render_in_flight when the config sets it, else 8 — capped by the free device memory.  A renderer the caller
     passed in gets its own in_flight back on return and its lanes' workspaces / raw buffers are released.
-    keep_maps: also return the host rgb_map of every frame (tests)."""
+    keep_maps: also return the host rgb_map of every frame (tests).
+    metrics: 'host' (default) = the float64 NumPy metrics below on host copies of the maps.  'device' = the outputs stay on the device and
+    an invr.evaluator.Evaluator (`evaluator`, or a fresh one: cfg.test_full metrics, no images) computes mse, psnr and SSIM there:
+    the returned dict also has 'ssim' (_run_evaluate_device)."""
     from collections import deque
+    if metrics not in ('host', 'device'):
+        raise ValueError("run_evaluate: metrics must be 'host' or 'device' (got %r)" % (metrics,))
     net.eval()
+    if metrics == 'device':
+        if keep_maps:
+            raise ValueError("run_evaluate: keep_maps returns host maps; metrics='device' leaves the maps on the device")
+        if in_flight is None:
+            cfg_v = getattr(net, 'cfg', {}).get('render_in_flight', None) if hasattr(getattr(net, 'cfg', None), 'get') else None
+            in_flight = int(cfg_v) if cfg_v else 8
+        if torch.device(device).type == 'cuda' and torch.cuda.is_available():
+            in_flight = _lanes_that_fit(max(1, int(in_flight)), device)
+        return _run_evaluate_device(net, batches, device, max(1, int(in_flight)), renderer, evaluator)
     renderer = renderer or Renderer(net)
     if in_flight is None:
         cfg_v = getattr(net, 'cfg', {}).get('render_in_flight', None) if hasattr(getattr(net, 'cfg', None), 'get') else None
