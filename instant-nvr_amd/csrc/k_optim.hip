@@ -1,7 +1,7 @@
 // Row f1: the optimiser step of the training loop — torch.optim.Adam over every trainable tensor
 // (lib/train/optimizer.py:13-31: one parameter group per tensor, eps = cfg.train.eps = 1e-15).  torch's foreach
 // implementation cannot batch across parameter groups: ~8 element-wise launches per tensor x 186 tensors = 1.5 k
-// launches and 7 ms per step for the 286 M parameters of inb_377.  This is ONE launch: a flat list of 64 k-element
+// launches and 7 ms per step for the 286 M parameters of inb_377.  This is ONE launch: a flat list of 16384-element
 // chunks over all tensors (chunk -> tensor table built once by the host), single pass over param / grad / exp_avg /
 // exp_avg_sq = 28 B per parameter, the HBM floor of a dense Adam step.
 // Arithmetic of torch/optim/adam.py (_single_tensor_adam, amsgrad=False, maximize=False):
