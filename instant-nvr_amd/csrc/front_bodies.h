@@ -4,7 +4,6 @@
 // stream costs 10-17 us per edge under hipGraph replay on this runtime (gpurun_out/r4c: 74 us of a 0.56 ms ray shard), launches
 // that follow each other on one stream start back to back — so independent small kernels share a launch instead of a stream.
 #pragma once
-#include <stdlib.h>
 #include "pipeline.h"
 
 #define CULL_BLOCK 256
@@ -434,12 +433,8 @@ __device__ __forceinline__ void deform_slice_body(const GridDev& dg, const DfSli
     out[e] = make_float2(fmaf(tz, v1.x, uz * v0.x), fmaf(tz, v1.y, uz * v0.y));
 }
 
-static bool deform_slices_fit(const GridDev& dg, DfSliceInfo& si, int cbv) {
+static bool deform_slices_fit(const GridDev& dg, DfSliceInfo& si) {
     si.off[0] = 0;
     for (int l = 0; l < INVR_MAX_LEVELS; ++l) si.off[l + 1] = si.off[l] + (l < dg.L ? dg.res[l] * dg.res[l] : 0);
-    return dg.L == 8 && si.off[8] <= DF_SLICE_MAX && cbv < 10;
-}
-static int deform_cb() {
-    static int cbv = getenv("INVR_DF_CB") ? atoi(getenv("INVR_DF_CB")) : 2;
-    return cbv;
+    return dg.L == 8 && si.off[8] <= DF_SLICE_MAX;
 }

@@ -362,7 +362,8 @@ static int render_impl(const InvrScene* scene, const InvrModel* model,
     // blocks of 8192 ray-samples.  Every training forward — invr_train_fwd / invr_geometry_fwd, and the op-by-op path's
     // invr_render_fwd calls, which carry jitter or ask for the weights — keeps the reference's ray-major row order (its per-row
     // noise and its (Na*P, .) outputs are defined on it).
-    static const int order_env = getenv("INVR_ORDER") ? atoi(getenv("INVR_ORDER")) : 1;      // (0 = ray-major everywhere: A/B switch, tools/ab_order.sh)
+    // INVR_ORDER is the library's only runtime switch (0 = ray-major everywhere: tools/ab_order.sh, tests/test_gpu_fullsize.py)
+    static const int order_env = getenv("INVR_ORDER") ? atoi(getenv("INVR_ORDER")) : 1;
     if (order_env && may_reorder && !wpts && !jitter && !weights && n_samples >= 8 && n_samples <= 1024 && (n_samples & (n_samples - 1)) == 0) {
         w.ord_cols = n_samples / 8;
         w.ord_rows = 1024 / w.ord_cols;
@@ -379,15 +380,11 @@ static int render_impl(const InvrScene* scene, const InvrModel* model,
     // under hipGraph replay cost more than the kernels it hid.
     INVR_HIP(hipMemsetAsync(w.counters, 0, counters_ints(w.n_groups) * sizeof(int32_t), st));
     GridDev dgrid = make_grid_dev(&model->deform_grid);
-    // ablation switches: the environment is read once per process, not per frame
-    static const bool no_voxmask = getenv("INVR_NO_VOXMASK") != nullptr, no_voxcls = getenv("INVR_NO_VOXCLS") != nullptr,
-                      no_merge = getenv("INVR_NO_MERGE") != nullptr;
     {
         ProfStage ps(INVR_STAGE_CULL, st);
         int have_cells = 0, flags_done = 0;
         if (launch_front_scene(a, w, dgrid, &have_cells, st)) return 1;
-        if (no_voxmask) w.knn.voxmask = nullptr;
-        if (!have_cells || no_voxcls) { w.knn.voxcls = nullptr; w.knn.voxmask = nullptr; }
+        if (!have_cells) { w.knn.voxcls = nullptr; w.knn.voxmask = nullptr; }
         else if (launch_front_cull(a, w, &flags_done, st)) return 1;
         if (w.knn.voxcls && !flags_done && launch_knn_voxel_class(a, w, st)) return 1;      // (small calls: the cull runs unmasked)
         if (launch_cull(a, w, max_active, have_cells != 0, flags_done != 0, st)) return 1;
@@ -405,8 +402,8 @@ static int render_impl(const InvrScene* scene, const InvrModel* model,
     if (!geometry_only) {
         // The five parts in one encoder launch and one launch per MLP phase (stage times are booked on part 0).  Eval reads the
         // row-sum tables; the training forward / eval without row sums read the trainable 64-byte rows — a part's 1e4-5e4 pairs
-        // make short, latency-bound launches, so the parts also run side by side there (the profiler and INVR_NO_MERGE keep
-        // per-part encoder launches, stage times per part).
+        // make short, latency-bound launches, so the parts also run side by side there (the profiler keeps per-part
+        // encoder launches, stage times per part).
         bool row_sums = true;
         for (int p = 0; p < INVR_NUM_PARTS; ++p) row_sums = row_sums && model->part[p].grid.row_sums != nullptr;
         EncodeAllArgs ea;
@@ -421,7 +418,7 @@ static int render_impl(const InvrScene* scene, const InvrModel* model,
         ea.counts = ma.counts = w.counters + CNT_PAIRS;
         ea.stride = ma.stride = w.lcap; ea.cap = ma.cap = w.lcap;
         ma.wcnt = w.wcnt; ma.gcount = w.gcount; ma.n_active = w.counters + CNT_ACTIVE; ma.rgbw = w.rgbw; ma.aggr = scene->aggr;
-        if (no_merge || (g_prof_on && !row_sums)) {
+        if (g_prof_on && !row_sums) {
             for (int p = 0; p < INVR_NUM_PARTS; ++p) {
                 ProfStage ps(INVR_STAGE_ENCODE + p, st);
                 if (launch_part_encode(ea.g[p], w.l_x[p], w.lcap, w.counters + CNT_PAIRS + p, w.lcap, w.emb[p], st)) return 1;

@@ -8,7 +8,6 @@
 // The active list is in ray-major / sample-minor order, exactly the order torch.nonzero gives,
 // so the train-time (Na*P, .) layouts of resd/tpts/tocc keep the reference's row order.  Eval frames
 // (Workspace::ord_rows > 0) use the depth-windowed order of k_scan_blocks_win / k_compact_win below instead.
-#include <stdlib.h>
 #include "pipeline.h"
 
 #include "front_bodies.h"
@@ -176,8 +175,7 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_compact_win(RenderArgs a, Worksp
 int launch_cull_cells(const RenderArgs& a, const Workspace& w, hipStream_t st) {
     const VolDev& v = a.scene.pbw;
     const int64_t cells = (int64_t)v.dx * v.dy * v.dz;
-    static const bool no_mask = getenv("INVR_NO_CULLMASK") != nullptr;
-    if (cells > CULL_MASK_MAX || cells > VOXMASK_MAX_CELLS || no_mask) return 0;
+    if (cells > CULL_MASK_MAX || cells > VOXMASK_MAX_CELLS) return 0;
     hipLaunchKernelGGL(k_cull_cells, dim3((unsigned)cdiv(cells, 256)), dim3(256), 0, st, v, a.scene.thresh * (1.0f + 1e-5f), w.cullmask,
                        w.knn.live_cells, w.counters + CNT_LIVE, w.knn.voxcls);
     if (hipGetLastError() != hipSuccess) return 0;

@@ -11,7 +11,6 @@
 // summed with two quad-DPP adds, level results are staged per wave in LDS ([k][64 points]) and
 // flushed as coalesced 256-byte rows into the SoA embedding buffer the MLP kernel consumes.
 // Two points are processed per iteration to keep 16 row fetches in flight per wave.
-#include <stdlib.h>
 #include "pipeline.h"
 #include "grid_generic.h"
 
@@ -347,9 +346,6 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_rows_all(EncodeAllArg
 //   d out_l / d t_a             = sum_k (+-)(w_b w_c) S_k,  S_k = sum_f table[row_k][f]   (needs the rows again)
 // Small dense levels (<= BWD_SMALL_ROWS rows) are accumulated per workgroup in LDS: a training patch
 // sends ~1e5 pairs through 8..1000-row coarse levels and would serialise on global atomics.
-#ifndef ENCB_EXP
-#define ENCB_EXP 0
-#endif
 #define BWD_SMALL_ROWS 1100
 #define BWD_SMALL_FLOATS 6144
 #define BWD_CACHE 4096
@@ -449,12 +445,6 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
                 const unsigned old = atomicCAS(&ckey[slot], 0xFFFFFFFFu, key);
                 if (old == 0xFFFFFFFFu || old == key) { atomicAdd(&cval[slot], vsum); return; }
             }
-#if ENCB_EXP == 1          // experiment (WRONG results): no global atomics — the kernel's floor without them
-            return;
-#elif ENCB_EXP == 2        // experiment (results only right if one XCD owns the row): the add performed in the issuing XCD's L2
-            __hip_atomic_fetch_add(gtb + (size_t)r * gstride, vsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            return;
-#endif
             unsafeAtomicAdd(gtb + (size_t)r * gstride, vsum);               // column 0 = row scalar
         };
         // the rows and corner weights of point j (quad-shared index math), and its eight row quarters
@@ -575,14 +565,14 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
     }
 }
 
+#define ENCB_GRID 512           // persistent: 2 workgroups per CU (79 KB of LDS each)
 static int launch_part_encode_bwd_io(const GridDev& g, const EncBwdIO& io_in, hipStream_t st) {
     const EncBwdIO& io = io_in;
     const int64_t n = io.n_host;                             // the count or its upper bound (device count given)
     int tp = 64;
     while (tp > 16 && n / tp < 4096) tp >>= 1;
     int64_t tiles = cdiv(n, (int64_t)tp * ENC_WAVES);
-    static const int gmax = getenv("INVR_ENCB_GRID") ? atoi(getenv("INVR_ENCB_GRID")) : 512;      // persistent: 2 workgroups per CU (79 KB of LDS each)
-    unsigned grid = (unsigned)(tiles < gmax ? (tiles > 0 ? tiles : 1) : gmax);
+    unsigned grid = (unsigned)(tiles < ENCB_GRID ? (tiles > 0 ? tiles : 1) : ENCB_GRID);
     hipLaunchKernelGGL(k_part_encode_bwd, dim3(grid), dim3(ENC_BLOCK), 0, st, g, io);
     INVR_LAUNCH_CHECK();
     return 0;
@@ -613,15 +603,10 @@ int launch_part_encode_bwd_lists(const GridDev& g, const float* x_soa, const flo
 // pairs of the list (eval frames: one depth slab of a few neighbouring rays, k_cull.hip; else consecutive samples of a ray), so neighbouring lanes fall into the
 // same / adjacent 64-byte lines; the level constants are wave-uniform (scalar registers).
 #define RS_BLOCK 256
-#ifndef ENC_X2
-#define ENC_X2 1          // A/B round 5: encoder 0.553 -> 0.542 ms, frame -1.1 % (gpurun_out/r5h), bit-identical
-#endif
-#ifndef ENC_MOD1R
-#define ENC_MOD1R 1       // A/B round 5: encoder stage 0.534 -> 0.524 ms (gpurun_out/r5o), bit-identical
-#endif
-#ifndef ENC_HOIST
-#define ENC_HOIST 1       // A/B round 5: encoder stage 0.538 -> 0.528 ms (gpurun_out/r5i), bit-identical
-#endif
+// Kept after the A/Bs of round 5 (run tags as in the note below), each bit-identical to the form it replaced:
+//  - one 8-byte load for the two x corners of a hashed level when their rows are adjacent: encoder 0.553 -> 0.542 ms, frame -1.1 % (r5h)
+//  - the one-round 24-bit modulo (GridDev.mod1r): encoder stage 0.534 -> 0.524 ms (r5o)
+//  - div_exact's range test hoisted to once per tile (k_part_encode_rs_xcd): encoder stage 0.538 -> 0.528 ms (r5i)
 // (Measured and not kept, round 5: both levels' gathers + the next tile's coordinates in flight at once — a prepare / fetch / finish
 //  split of the level — 93 instead of 69 VGPRs, 5 instead of 7 waves per SIMD: 0.540 -> 0.588 ms, gpurun_out/r5k.)
 // one level of one point through the row-sum table (wave-uniform level l)
@@ -654,9 +639,9 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
         level_corners_fast(y, cell, rcell, res, c0y, c1y, ty);
         level_corners_fast(z, cell, rcell, res, c0z, c1z, tz);
     } else {
-    level_corners(x, cell, rcell, res, c0x, c1x, tx);
-    level_corners(y, cell, rcell, res, c0y, c1y, ty);
-    level_corners(z, cell, rcell, res, c0z, c1z, tz);
+        level_corners(x, cell, rcell, res, c0x, c1x, tx);
+        level_corners(y, cell, rcell, res, c0y, c1y, ty);
+        level_corners(z, cell, rcell, res, c0z, c1z, tz);
     }
     unsigned row[8];
     const float* tab;
@@ -677,7 +662,6 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
             // back into [0, T) (T > 2^14 > 2 |delta|: host-checked, GridDev.xdelta), instead of four
             // more 3-round reductions
             const uint32_t m = (uint32_t)c0x ^ (uint32_t)c1x;
-#if ENC_MOD1R
             if (g.mod1r) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -690,17 +674,17 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
                     r1 = min(r1, r1 - (uint32_t)g.T);
                     row[4 + k] = r1;
                 }
-            } else
-#endif
+            } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint64_t X = hx[0] ^ hy[(k >> 1) & 1] ^ hz[k & 1];
-                const uint32_t r0 = hash_mod24_2r(X, g.mod_k, g.mod_c, (uint32_t)g.T);
-                row[k] = r0;
-                uint32_t r1 = r0 + m - 2u * ((uint32_t)X & m);
-                r1 = min(r1, r1 + (uint32_t)g.T);
-                r1 = min(r1, r1 - (uint32_t)g.T);
-                row[4 + k] = r1;
+                for (int k = 0; k < 4; ++k) {
+                    const uint64_t X = hx[0] ^ hy[(k >> 1) & 1] ^ hz[k & 1];
+                    const uint32_t r0 = hash_mod24_2r(X, g.mod_k, g.mod_c, (uint32_t)g.T);
+                    row[k] = r0;
+                    uint32_t r1 = r0 + m - 2u * ((uint32_t)X & m);
+                    r1 = min(r1, r1 + (uint32_t)g.T);
+                    r1 = min(r1, r1 - (uint32_t)g.T);
+                    row[4 + k] = r1;
+                }
             }
         } else if (g.mod24) {
 #pragma unroll
@@ -734,7 +718,7 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
             for (int j = 0; j < 4; ++j) pr[j] = make_float2(g_enc_tab[bb[j] + z0], g_enc_tab[bb[j] + z0 + 1u]);       // ds_read2_b32
         } else {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) __builtin_memcpy(&pr[j], tab + bb[j] + z0, sizeof(float2));   // 4-byte aligned 8-byte load (global_load_dwordx2)
+            for (int j = 0; j < 4; ++j) __builtin_memcpy(&pr[j], tab + bb[j] + z0, sizeof(float2));   // 4-byte aligned 8-byte load (global_load_dwordx2)
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -753,7 +737,6 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
         return acc;
     }
     float v[8];
-#if ENC_X2
     if (g.xdelta) {
         // x's hash prime is 1: the c1x corner of an (y, z) corner pair sits at row r0 + delta, and delta = +-1 for ~60 % of the pairs
         // (always when c0x is even: X ^ 1 = X +- 1).  Those lanes fetch BOTH rows with one 8-byte load at min(r0, r1); the others issue
@@ -780,11 +763,9 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
             v[k] = adj[k] ? (up ? pr[k].x : pr[k].y) : s0[k];
             v[4 + k] = adj[k] ? (up ? pr[k].y : pr[k].x) : s1[k];
         }
-    } else
-#endif
-    {
+    } else {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = tab[row[k]];
+        for (int k = 0; k < 8; ++k) v[k] = tab[row[k]];
     }
     const float ux = 1.0f - tx, uy = 1.0f - ty, uz = 1.0f - tz;
     float acc = 0.0f;
@@ -815,18 +796,12 @@ __global__ __launch_bounds__(RS_BLOCK) void k_part_encode_rs(GridDev g, const fl
     encode_rs_part(g, rs, xs, stride, *count, cap, emb);
 }
 
-// all five parts in ONE persistent launch: a workgroup walks its share of part 0, then of part 1, ... without a
-// device-wide drain between parts (5 launches of this size spend ~15 us each on ramp-up and tail)
-__global__ __launch_bounds__(RS_BLOCK) void k_part_encode_rs_all(EncodeAllArgs a) {
-    for (int p = 0; p < INVR_NUM_PARTS; ++p)
-        encode_rs_part(a.g[p], a.g[p].row_sums, a.xs[p], a.stride, a.counts[p], a.cap, a.emb[p]);
-}
-
-// XCD-partitioned variant: workgroups are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8), each with
+// All five parts in ONE persistent launch: a workgroup walks its share of part 0, then of part 1, ... without a
+// device-wide drain between parts (5 launches of this size spend ~15 us each on ramp-up and tail).
+// XCD-partitioned: workgroups are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8), each with
 // its own 4 MB L2.  Level group lg = blockIdx.x & 7 handles levels {lg, 15 - lg} (rotated per part so that the
 // heavier hashed pairs do not always land on the same XCD) of EVERY pair tile: an XCD's L2 then only ever sees one
 // eighth of the row-sum tables (8.5 MB of 68 MB) instead of all of them.
-template <bool use_lds>
 __global__ __launch_bounds__(RS_BLOCK) void k_part_encode_rs_xcd(EncodeAllArgs a) {
     const int xcd = blockIdx.x & 7;
     const int tstride = gridDim.x >> 3;
@@ -847,35 +822,29 @@ __global__ __launch_bounds__(RS_BLOCK) void k_part_encode_rs_xcd(EncodeAllArgs a
         const int hstart = g.separate_dense ? g.start_hash : 0;
         // level la in LDS when it is a dense level of at most ENC_LDS_ROWS rows (wave-uniform; res^3 rows, (:124-129))
         const int res_a = g.res[la];
-        const bool lds_a = use_lds && la < g.start_hash && (int64_t)res_a * res_a * res_a <= ENC_LDS_ROWS && tile0 * RS_BLOCK < cnt;
-        if (use_lds) __syncthreads();                 // (the previous part's look-ups are done before its table is replaced)
+        const bool lds_a = la < g.start_hash && (int64_t)res_a * res_a * res_a <= ENC_LDS_ROWS && tile0 * RS_BLOCK < cnt;
+        __syncthreads();                 // (the previous part's look-ups are done before its table is replaced)
         if (lds_a) {
             const float* __restrict__ src = g.separate_dense ? rs + g.dense_off[la] : rs + (int64_t)la * g.T;
             const int rows = res_a * res_a * res_a;
             for (int t = threadIdx.x; t < rows; t += RS_BLOCK) g_enc_tab[t] = src[t];
             if (threadIdx.x < 2) g_enc_tab[rows + threadIdx.x] = 0.0f;          // (the pair read of the last row's z0 = res - 2 ends at rows - 1: never read, kept defined)
         }
-        if (use_lds) __syncthreads();
+        __syncthreads();
         for (int64_t i = tile0 * RS_BLOCK + threadIdx.x; i < cnt; i += (int64_t)tstride * RS_BLOCK) {
             const float x = (xs[i] - b0x) / ex, y = (xs[a.stride + i] - b0y) / ey, z = (xs[2 * a.stride + i] - b0z) / ez;   // :112
             if (lg < 3) emb[(int64_t)lg * a.cap + i] = lg == 0 ? x : (lg == 1 ? y : z);
             else if (lg == 3) emb[(int64_t)(EMB_K - 1) * a.cap + i] = 0.0f;          // pad column
-#if ENC_HOIST
             // div_exact's range test, once per tile instead of once per quotient (the coordinates are the same for every level)
             const bool okp = fabsf(x) > 8.7e-19f && fabsf(x) < 1.0e6f && fabsf(y) > 8.7e-19f && fabsf(y) < 1.0e6f && fabsf(z) > 8.7e-19f && fabsf(z) < 1.0e6f;
             const bool fast = __ballot(!okp) == 0ull;
             if (lds_a) {
                 if (fast && g.rcell[la] != 0.0f) emb[(int64_t)(3 + la) * a.cap + i] = level_rowsum<true, true>(g, rs, hstart, la, x, y, z);
                 else emb[(int64_t)(3 + la) * a.cap + i] = level_rowsum<false, true>(g, rs, hstart, la, x, y, z);
-            } else
-            if (fast && g.rcell[la] != 0.0f) emb[(int64_t)(3 + la) * a.cap + i] = level_rowsum<true>(g, rs, hstart, la, x, y, z);
+            } else if (fast && g.rcell[la] != 0.0f) emb[(int64_t)(3 + la) * a.cap + i] = level_rowsum<true>(g, rs, hstart, la, x, y, z);
             else emb[(int64_t)(3 + la) * a.cap + i] = level_rowsum<false>(g, rs, hstart, la, x, y, z);
             if (fast && g.rcell[lb] != 0.0f) emb[(int64_t)(3 + lb) * a.cap + i] = level_rowsum<true>(g, rs, hstart, lb, x, y, z);
             else emb[(int64_t)(3 + lb) * a.cap + i] = level_rowsum<false>(g, rs, hstart, lb, x, y, z);
-#else
-            emb[(int64_t)(3 + la) * a.cap + i] = level_rowsum(g, rs, hstart, la, x, y, z);
-            emb[(int64_t)(3 + lb) * a.cap + i] = level_rowsum(g, rs, hstart, lb, x, y, z);
-#endif
         }
     }
 }
@@ -937,16 +906,8 @@ int launch_part_encode_all(const EncodeAllArgs& a, hipStream_t st) {
         }
     }
     int64_t tiles = cdiv(a.cap, RS_BLOCK);
-    unsigned grid = (unsigned)(tiles < 256 * 8 ? (tiles > 0 ? tiles : 1) : 256 * 8);
-    static const int xcd_mode = getenv("INVR_ENC_XCD") ? atoi(getenv("INVR_ENC_XCD")) : 1;
-    if (xcd_mode) {
-        unsigned gx = (unsigned)(tiles * 8 < 256 * 8 ? (tiles > 0 ? tiles * 8 : 8) : 256 * 8);      // a multiple of 8
-        static const bool no_lds = getenv("INVR_ENC_NOLDS") != nullptr;                 // (A/B switch)
-        if (no_lds) hipLaunchKernelGGL(k_part_encode_rs_xcd<false>, dim3(gx), dim3(RS_BLOCK), 0, st, a);
-        else hipLaunchKernelGGL(k_part_encode_rs_xcd<true>, dim3(gx), dim3(RS_BLOCK), 0, st, a);
-    } else {
-        hipLaunchKernelGGL(k_part_encode_rs_all, dim3(grid), dim3(RS_BLOCK), 0, st, a);
-    }
+    unsigned gx = (unsigned)(tiles * 8 < 256 * 8 ? (tiles > 0 ? tiles * 8 : 8) : 256 * 8);      // a multiple of 8
+    hipLaunchKernelGGL(k_part_encode_rs_xcd, dim3(gx), dim3(RS_BLOCK), 0, st, a);
     INVR_LAUNCH_CHECK();
     return 0;
 }

@@ -33,7 +33,6 @@
 // LDS (persistent 1024-thread workgroups, one per CU); a wave draws tickets of 64 survivors, one thread per point: every vertex /
 // record read is a wave-uniform (broadcast) ds_read_b128, clusters and sub-clusters are pruned per wave with
 // lb(box) <= current 4th-best, distances of two vertices per packed-fp32 instruction, top-4 kept as 64-bit (distance, row) keys.
-#include <stdlib.h>
 #include "pipeline.h"
 #include "front_bodies.h"
 
@@ -553,21 +552,7 @@ struct KnnLds { int voff[INVR_NUM_PARTS], coff[INVR_NUM_PARTS], soff[INVR_NUM_PA
 // the 16 — 64 consecutive survivors are one depth slab of a few rays (ray-major order: depth segments of a few rays), and they differ widely in how many parts they
 // come near — 29 % of the kernel's wave time on a whole frame and 51 % on a 1/8 shard, tools/knn_phase_prof.py.  Now a wave
 // never waits for another one.)
-// KNN_DBG: ablation switch of the profiling builds only (tools/knn_phase_prof.sh: -DKNN_DBG=1 no exact scans, 2 seed cluster
-// only, 4 the sweep's box tests without its vertex scans, 8 vertex scans whose prefilter never passes — WRONG results); the shipped
-// library is compiled without it.
-#ifndef KNN_DBG
-#define KNN_DBG 0
-#endif
-#ifndef KNN_SUB4
-#define KNN_SUB4 2
-#endif
-#ifdef KNN_WPE          // experiment: a register budget that leaves room for another kernel's wave beside the workgroup's four per SIMD
-__global__ __launch_bounds__(KNN_T) __attribute__((amdgpu_waves_per_eu(KNN_WPE, KNN_WPE))) void k_knn_pairs(RenderArgs a, Workspace w) {
-#else
 __global__ __launch_bounds__(KNN_T) void k_knn_pairs(RenderArgs a, Workspace w) {
-#endif
-    constexpr int dbg = KNN_DBG;
     // all LDS is dynamic (a static __shared__ in front would misalign the float4 region, guide G17): vertices, then cluster records
     extern __shared__ __attribute__((aligned(16))) float4 lds_raw[];
     float4* lds = lds_raw + KNN_LDS_HDR;
@@ -604,7 +589,6 @@ __global__ __launch_bounds__(KNN_T) void k_knn_pairs(RenderArgs a, Workspace w) 
         for (int j = threadIdx.x; j < ncl * 8; j += KNN_T)            // (64 rows of 2 bytes = 8 float4 per cluster; mpad is a multiple of 64)
             lds[roff + L.voff[p] / 8 + j] = reinterpret_cast<const float4*>(ix.srow + (int64_t)p * ix.mpad)[j];
         for (int j = threadIdx.x; j < ncl * 3; j += KNN_T) lds[L.coff[p] + j] = ix.cl[(int64_t)p * ix.cpad * 3 + j];
-#if KNN_SUB4
         // the four sub-cluster boxes of a cluster TRANSPOSED, {lo.x[4], lo.y[4], lo.z[4], hi.x[4], hi.y[4], hi.z[4]} (6 of the cluster's 8
         // float4 slots): the sweep tests all four with packed-fp32 arithmetic, two boxes per instruction
         for (int j = threadIdx.x; j < ncl * 6; j += KNN_T) {
@@ -612,9 +596,6 @@ __global__ __launch_bounds__(KNN_T) void k_knn_pairs(RenderArgs a, Workspace w) 
             const float* g = reinterpret_cast<const float*>(ix.sub + (int64_t)p * ix.cpad * 8 + c * 8 + hi) + ax;     // box s at + s * 8 floats
             lds[L.soff[p] + c * 8 + r] = make_float4(g[0], g[8], g[16], g[24]);
         }
-#else
-        for (int j = threadIdx.x; j < ncl * 8; j += KNN_T) lds[L.soff[p] + j] = ix.sub[(int64_t)p * ix.cpad * 8 + j];
-#endif
     }
     __syncthreads();
     KP(6)
@@ -733,7 +714,7 @@ __global__ __launch_bounds__(KNN_T) void k_knn_pairs(RenderArgs a, Workspace w) 
             const bool unflagged = maybe ? (lb2 >= a.scene.near_hi2 && ub2 <= a.scene.band_lo2) : (c2 == 2);
             const bool scan = live && !is_far && !unflagged;
             if (live && is_far) farflags |= 1u << p;
-            if (__ballot(scan) == 0 || (dbg & 1)) continue;
+            if (__ballot(scan) == 0) continue;
             KP(2)
             KP_CNT(9)
             KP_MARK
@@ -765,9 +746,10 @@ __global__ __launch_bounds__(KNN_T) void k_knn_pairs(RenderArgs a, Workspace w) 
             const float qd = q2 - mm * mm * 1.9073486328125e-06f;
             // (lanes that do not scan this part — decided cell, far, provably unflagged — never pass the prefilter: they used to keep a
             // top-4 of their own and pulled the wave into the insert branch for it)
-            float thr = (scan && !(dbg & 8)) ? t.worst() - qd : -__builtin_inff();
+            float thr = scan ? t.worst() - qd : -__builtin_inff();
 #pragma unroll 1
-            for (int k = full ? 1 : 0; (seed_c + k < ncl || seed_c - k >= 0) && !(dbg & 2); ++k) {
+            for (int k = full ? 1 : 0; ; ++k) {
+                if (seed_c + k >= ncl && seed_c - k < 0) break;          // both sides have left the part's clusters
 #pragma unroll 1
                 for (int side = 0; side < (k ? 2 : 1); ++side) {
                     const int c = side ? seed_c - k : seed_c + k;
@@ -776,7 +758,6 @@ __global__ __launch_bounds__(KNN_T) void k_knn_pairs(RenderArgs a, Workspace w) 
                     const bool need = scan && aabb_dist2(px, py, pz, lds_ld4(cl + c * 3), lds_ld4(cl + c * 3 + 1)) <= t.worst();
                     if (__ballot(need) == 0) continue;
                     KP_CNT(10)
-#if KNN_SUB4
                     // the box distances of the cluster's four sub-clusters at once: six record reads in flight instead of four round
                     // trips of two, two boxes per packed instruction — each value the operations of aabb_dist2 in its order, so a
                     // sub-cluster is scanned exactly when the one-at-a-time test (against the 4th-best of that moment) scans it
@@ -797,30 +778,13 @@ __global__ __launch_bounds__(KNN_T) void k_knn_pairs(RenderArgs a, Workspace w) 
                             lbs[2 * h] = l2.x; lbs[2 * h + 1] = l2.y;
                         }
                     }
-                    // (rolled: four inlined copies of the scan are +40 % code in a kernel that sits at the instruction cache's size;
-                    // s4 is wave-uniform, the select is three scalar-conditioned moves)
-#if KNN_SUB4 == 2
 #pragma unroll
-#else
-#pragma unroll 1
-#endif
                     for (int s4 = 0; s4 < 4; ++s4) {
-                        const float lb_s = s4 == 0 ? lbs[0] : s4 == 1 ? lbs[1] : s4 == 2 ? lbs[2] : lbs[3];
-                        const bool need_s = need && lb_s <= t.worst();
-                        if (__ballot(need_s) == 0) continue;
-                        KP_CNT(11)
-                        if (dbg & 4) continue;
-                        scan_sub16_pf(sv + c * 64 + s4 * 16, rw + c * 32 + s4 * 8, ax2, ay2, az2, px2, py2, pz2, qd, thr, t KP_SCAN_PASS);
-                    }
-#else
-#pragma unroll 1
-                    for (int s4 = 0; s4 < 4; ++s4) {
-                        const bool need_s = need && aabb_dist2(px, py, pz, lds_ld4(sb + c * 8 + s4 * 2), lds_ld4(sb + c * 8 + s4 * 2 + 1)) <= t.worst();
+                        const bool need_s = need && lbs[s4] <= t.worst();
                         if (__ballot(need_s) == 0) continue;
                         KP_CNT(11)
                         scan_sub16_pf(sv + c * 64 + s4 * 16, rw + c * 32 + s4 * 8, ax2, ay2, az2, px2, py2, pz2, qd, thr, t KP_SCAN_PASS);
                     }
-#endif
                 }
             }
             KP(3)
@@ -1220,14 +1184,13 @@ int launch_front_scene(const RenderArgs& a, const Workspace& w, const GridDev& d
     f.s = a.scene; f.ix = w.knn;
     const VolDev& v = a.scene.pbw;
     const int64_t cells = (int64_t)v.dx * v.dy * v.dz;
-    static const bool no_mask = getenv("INVR_NO_CULLMASK") != nullptr;
-    *have_cells = !(cells > CULL_MASK_MAX || cells > VOXMASK_MAX_CELLS || no_mask);
+    *have_cells = !(cells > CULL_MASK_MAX || cells > VOXMASK_MAX_CELLS);
     f.thresh_hi = a.scene.thresh * (1.0f + 1e-5f); f.cullmask = w.cullmask; f.n_live = w.counters + CNT_LIVE;
     f.n_cells_wg = *have_cells ? (int)cdiv(cells, PREP_T) : 0;
     f.vmat_m = a.scene.M < w.knn.mpad ? a.scene.M : w.knn.mpad;
     f.n_vmat_wg = (int)cdiv(f.vmat_m, PREP_T);
     f.dg = dg; f.dslice = w.dslice;
-    f.n_slice_wg = deform_slices_fit(dg, f.si, deform_cb()) ? (int)cdiv(f.si.off[8], PREP_T) : 0;
+    f.n_slice_wg = deform_slices_fit(dg, f.si) ? (int)cdiv(f.si.off[8], PREP_T) : 0;
     const unsigned grid = (unsigned)(INVR_NUM_PARTS + f.n_cells_wg + f.n_vmat_wg * INVR_NUM_PARTS + f.n_slice_wg);
     hipLaunchKernelGGL(k_front_scene, dim3(grid), dim3(PREP_T), PREP_LDS_BYTES, st, f);
     INVR_LAUNCH_CHECK();
@@ -1266,17 +1229,15 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_front_cull(RenderArgs a, Workspa
 int launch_front_cull(const RenderArgs& a, const Workspace& w, int* done, hipStream_t st) {
     const VolDev& v = a.scene.pbw;
     const int64_t cells = (int64_t)v.dx * v.dy * v.dz, nb = cdiv(a.N, CULL_TILE);
-    static const bool no_voxcls = getenv("INVR_NO_VOXCLS") != nullptr;
     *done = 0;
-    if (!(a.N >= 4 * cells) || no_voxcls) return 0;
+    if (!(a.N >= 4 * cells)) return 0;
     const unsigned gx = voxel_class_grid(v);
     const double inv_S = 1.0 / (double)a.S;
     const float lin_step = 1.0f / (float)(a.S - 1);
     const bool fast = !a.wpts && !a.jitter && a.N < (1ll << 31) && cells * v.c < (1ll << 31) && a.S >= 2 &&
                       v.dx <= 1024 && v.dy <= 1024 && v.dz <= 1024;      // (front_bodies.h: the pre-test's error bound)
     const unsigned grid = gx * INVR_NUM_PARTS + (unsigned)nb;
-    static const bool no_d1 = getenv("INVR_NO_CULL_D1") != nullptr;
-    if (fast && (a.S & 3) == 0 && !a.z_vals && !no_d1) {
+    if (fast && (a.S & 3) == 0 && !a.z_vals) {
         // the cell mask dilated by one cell (k_dilate_mask, ~3 us between the two front launches): a thread of the RAY4 cull drops
         // its four samples on ONE look-up when the whole segment provably stays inside dead cells (front_bodies.h)
         Workspace w2 = w;

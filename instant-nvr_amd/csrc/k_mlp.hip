@@ -1,34 +1,24 @@
-// K6: the two tiny Softplus MLPs of one body part on the fp32 matrix cores.
+// K6: the two tiny Softplus MLPs of one body part on the matrix cores.
 // Replaces part_base_network.Network.forward after the encoder (part_base_network.py:44-63):
 //   h   = occMLP(emb19)            19 -> 64 -> 17          (Softplus between linears)
 //   occ = 1 - exp(-softplus(h[0])) ; feat = h[1:17]
 //   rgb = sigmoid(rgbMLP([emb19, dirPE27, feat16, latent8]))   70 -> 64 (-> 64) -> 3
 //
-// fp32 parity (1e-4 per pixel) rules out bf16/fp16 MFMA inputs, so the layers run on
-// v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains, MI355X_MICROARCH "Matrix cores").
+// fp32 parity (1e-4 per pixel) rules out plain bf16/fp16 MFMA inputs.  The occupancy MLP's layers run on
+// v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains, MI355X_MICROARCH "Matrix cores"); the colour MLP's two 64-wide
+// layers run on v_mfma_f32_16x16x32_bf16 as exact 3-way bf16 splits of weights and activations (six products per
+// tile with fp32 accumulation: fp32 accuracy at 0.58x the time, see mlp_common.h).
 // Orientation: D^T = W . X^T — weights are the A operand (M = 16 output features per tile),
 // 16 (point,part) pairs are the N columns.  With that orientation the accumulator registers of
 // one layer ARE the B operands of the next (lane group g = lane>>4 holds features 16*mt+4g+r of
 // pair lane&15 in register r), provided the next layer's weights are stored in the matching
 // K order — so activations never leave registers between layers.  Weights are re-ordered into
-// that per-(k-step, m-tile, lane) order while they are staged into LDS (46 KB per part).
+// that per-(k-step, m-tile, lane) order while they are staged into LDS (59 KB per part).
 // The 1-wide / 3-wide heads (occupancy logit, rgb out) are 16-term VALU dot products plus two
 // cross-lane adds instead of wasting 15/16 of an MFMA tile.
-#include <stdlib.h>
 #include "pipeline.h"
 
 #include "mlp_common.h"
-
-// compile-time ablations for profiling experiments (tools/mlp_ablate.sh): 1 no activations, 2 no MFMA, 3 no LDS weight reads
-#ifndef MLP_DBG
-#define MLP_DBG 0
-#endif
-#if MLP_DBG == 2
-#define mfma4(a, b, c) ((c) + (f32x4){(a) * (b), 0.f, 0.f, 0.f})
-#endif
-#if MLP_DBG == 1
-#define softplus4_log2(v) (v)
-#endif
 
 // One 16-pair column block of a wave: inputs, activations and outputs stay in registers from the embedding to [rgb, occ].
 struct MlpCol {
@@ -38,12 +28,9 @@ struct MlpCol {
     f32x4 feat;                 // occ features 1..16 (true scale)
     float occ;
     float k5[11];               // rgb layer-1 k-slots 5..15: sin/cos (6), d (1), feat (4)
-#if MLP_BF16
     mlp_bf16x8 sh[2], sm[2], sl[2];   // the 16 inputs of the next 64-wide layer (k-slots s = 8 kb + j) as bf16 hi / mid / lo terms
-#endif
 };
 
-#if MLP_BF16
 // One 64 -> 64 (or 64-slot -> 64) layer of a column block on the bf16 matrix pipe: six products per (m-tile, k-block), smallest first.
 __device__ __forceinline__ void bf16x3_layer(const float* lds_w, const float* lds_b, int lane, int g, const MlpCol& c, f32x4* out) {
     const mlp_bf16x8* w = reinterpret_cast<const mlp_bf16x8*>(lds_w);
@@ -72,7 +59,6 @@ __device__ __forceinline__ void bf16x3_split_h(MlpCol& c) {
         bf16_split3x8(v, c.sh[kb], c.sm[kb], c.sl[kb]);
     }
 }
-#endif
 
 // The stages of the two MLPs for ONE column block.  mlp_part runs two column blocks per wave SKEWED by one stage, so that in
 // every scheduling region the matrix-core instructions of one block sit beside the vector instructions (activation, view-
@@ -95,9 +81,7 @@ __device__ __forceinline__ void st_act(MlpCol& c) {
 // activation of a colour-MLP layer whose output feeds another 64-wide layer (rgb1 of the three-layer nets): + the bf16 split
 __device__ __forceinline__ void st_act_split(MlpCol& c) {
     st_act(c);
-#if MLP_BF16
     bf16x3_split_h(c);
-#endif
 }
 __device__ __forceinline__ void st_occ2(const float* lds, int lane, int g, MlpCol& c) {       // features 1..16 on MFMA, logit 0 on VALU
     c.feat = bias4(lds + O_B_OCC2, 0, g);
@@ -121,52 +105,20 @@ __device__ __forceinline__ void st_rgb_in(MlpCol& c, int g, float fmul) {
     c.k5[6] = g == 0 ? c.dv[0] : (g == 1 ? c.dv[1] : (g == 2 ? c.dv[2] : 0.0f));
 #pragma unroll
     for (int r = 0; r < 4; ++r) c.k5[7 + r] = c.feat[r];
-#if MLP_BF16
-    {   // the 16 k-slots of rgb layer 1 (s < 5: embedding, s >= 5: k5) as split bf16 inputs
-        float v0[8] = {c.eb[0], c.eb[1], c.eb[2], c.eb[3], c.eb[4], c.k5[0], c.k5[1], c.k5[2]};
-        float v1[8] = {c.k5[3], c.k5[4], c.k5[5], c.k5[6], c.k5[7], c.k5[8], c.k5[9], c.k5[10]};
-        bf16_split3x8(v0, c.sh[0], c.sm[0], c.sl[0]);
-        bf16_split3x8(v1, c.sh[1], c.sm[1], c.sl[1]);
-    }
-#endif
+    // the 16 k-slots of rgb layer 1 (s < 5: embedding, s >= 5: k5) as split bf16 inputs
+    float v0[8] = {c.eb[0], c.eb[1], c.eb[2], c.eb[3], c.eb[4], c.k5[0], c.k5[1], c.k5[2]};
+    float v1[8] = {c.k5[3], c.k5[4], c.k5[5], c.k5[6], c.k5[7], c.k5[8], c.k5[9], c.k5[10]};
+    bf16_split3x8(v0, c.sh[0], c.sm[0], c.sl[0]);
+    bf16_split3x8(v1, c.sh[1], c.sm[1], c.sl[1]);
 }
 __device__ __forceinline__ void st_rgb1(const float* lds, int lane, int g, MlpCol& c) {
-#if MLP_BF16
     bf16x3_layer(lds + O_W_RGB1, lds + O_B_RGB1, lane, g, c, c.h);
-    return;
-#endif
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) c.h[mt] = bias4(lds + O_B_RGB1, mt, g);
-#pragma unroll
-    for (int s = 0; s < RGB1F_STEPS; ++s) {
-        const float4 a = *reinterpret_cast<const float4*>(lds + O_W_RGB1 + (s * 64 + lane) * 4);
-        const float b = s < EMB_STEPS ? c.eb[s < EMB_STEPS ? s : 0] : c.k5[s >= EMB_STEPS ? s - EMB_STEPS : 0];
-        c.h[0] = mfma4(a.x, b, c.h[0]); c.h[1] = mfma4(a.y, b, c.h[1]);
-        c.h[2] = mfma4(a.z, b, c.h[2]); c.h[3] = mfma4(a.w, b, c.h[3]);
-    }
 }
 __device__ __forceinline__ void st_rgb2(const float* lds, int lane, int g, MlpCol& c) {
-#if MLP_BF16
-    {
-        f32x4 o[4];
-        bf16x3_layer(lds + O_W_RGB2, lds + O_B_RGB2, lane, g, c, o);
+    f32x4 o[4];
+    bf16x3_layer(lds + O_W_RGB2, lds + O_B_RGB2, lane, g, c, o);
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) c.h[mt] = o[mt];
-        return;
-    }
-#endif
-    f32x4 h2[4];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) h2[mt] = bias4(lds + O_B_RGB2, mt, g);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-        const float4 a = *reinterpret_cast<const float4*>(lds + O_W_RGB2 + (s * 64 + lane) * 4);
-        const float b = c.h[s >> 2][s & 3];
-        h2[0] = mfma4(a.x, b, h2[0]); h2[1] = mfma4(a.y, b, h2[1]);
-        h2[2] = mfma4(a.z, b, h2[2]); h2[3] = mfma4(a.w, b, h2[3]);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) c.h[mt] = h2[mt];
+    for (int mt = 0; mt < 4; ++mt) c.h[mt] = o[mt];
 }
 __device__ __forceinline__ float4 st_head(const float* lds, int g, const MlpCol& c) {          // rgb head 64 -> 3, sigmoid
     float o[3];
@@ -176,17 +128,10 @@ __device__ __forceinline__ float4 st_head(const float* lds, int g, const MlpCol&
 }
 #define MLP_FENCE() __builtin_amdgcn_sched_barrier(0)
 // matrix / vector instruction mix of the colour-MLP regions below (bf16 x 3: 48 MFMAs of 16 cycles + the split of the next inputs)
-#if MLP_BF16
 #define RGB_MFMAS 48
 #define RGB_V 3
 #define RGB_MFMAS_IN 48
 #define RGB_V_IN 3
-#else
-#define RGB_MFMAS 64
-#define RGB_V 1
-#define RGB_MFMAS_IN 30
-#define RGB_V_IN 1
-#endif
 // Interleave directive for one scheduling region (between two MLP_FENCEs): N_MFMA groups of {1 matrix instruction, V vector
 // instructions} — the vector work of the other column block is issued in the shadows of this block's MFMAs (<= 5 single-issue
 // VALU fit beside a 32-cycle fp32 MFMA; MI355X_MICROARCH.md).  LDS reads of the weights float freely.
@@ -714,9 +659,7 @@ __device__ __forceinline__ void rgb_part(float* lds, const MlpAllArgs& a, const 
     }
 }
 
-#ifndef RGB_WPS
-#define RGB_WPS (MLP_BF16 ? 2 : 3)          // workgroups per CU the colour kernel is compiled / launched for (bf16 x 3: 59 KB of LDS each)
-#endif
+#define RGB_WPS 2          // workgroups per CU the colour kernel is compiled / launched for (bf16 x 3: 59 KB of LDS each)
 template <bool MEAN>
 __global__ __launch_bounds__(MLP_BLOCK, RGB_WPS) void k_part_rgb_all(MlpAllArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
@@ -794,6 +737,7 @@ int launch_part_mlp_all(const MlpAllArgs& a, const Workspace& w, hipStream_t st)
     return 0;
 }
 
+#define MLP_WPS 3          // workgroups per CU the single-part kernel is launched for
 int launch_part_mlp(const PartMlpDev& pm, const float* emb, const float* d_soa, int64_t stride,
                     const int32_t* count, int64_t cap, float4* raw_direct, hipStream_t st) {
     const MlpDev& o = pm.occ;
@@ -808,8 +752,7 @@ int launch_part_mlp(const PartMlpDev& pm, const float* emb, const float* d_soa, 
     }
     const int64_t per_block = (MLP_BLOCK / 64) * MLP_CB * 16;
     int64_t tiles = cdiv(cap, per_block);
-    static int wpb = getenv("INVR_MLP_BPC") ? atoi(getenv("INVR_MLP_BPC")) : 3;
-    unsigned grid = (unsigned)(tiles < 256 * wpb ? (tiles > 0 ? tiles : 1) : 256 * wpb);
+    unsigned grid = (unsigned)(tiles < 256 * MLP_WPS ? (tiles > 0 ? tiles : 1) : 256 * MLP_WPS);
     if (r.n_linear == 3)
         hipLaunchKernelGGL(k_part_mlp<3>, dim3(grid), dim3(MLP_BLOCK), 0, st, pm, emb, d_soa, stride, count, cap, raw_direct);
     else

@@ -11,12 +11,7 @@
 static_assert(sizeof(float*) == 8, "64-bit");
 #define ADAM_BLOCK 256
 #define ADAM_CHUNK 16384            // elements per workgroup
-#ifndef ADAM_NT
-#define ADAM_NT 1
-#endif
-#ifndef ADAM_UNROLL
-#define ADAM_UNROLL 4
-#endif
+#define ADAM_UNROLL 4               // float4 per array and thread in flight
 
 struct AdamTensor {                 // device-resident table, one entry per tensor that has a gradient this step (InvrAdamTensor)
     float* p; const float* g; float* m; float* v;
@@ -57,24 +52,16 @@ __global__ __launch_bounds__(ADAM_BLOCK) void k_adam(const AdamTensor* __restric
     // 28 B per parameter stream through this kernel once per step and nothing of it is read again before the next step has streamed
     // another 6.9 GB through the caches: nontemporal loads / stores (no L2 / Infinity-Cache allocation), and ADAM_UNROLL float4 per
     // array and thread in flight before the first use (the loop form issued one float4 per array, waited, computed, stored: too
-    // few bytes in flight per CU for the HBM latency).  ADAM_NT=0 / ADAM_UNROLL=1: the round-4 form (A/B builds).
+    // few bytes in flight per CU for the HBM latency).
     auto ld4 = [](const float* q) -> float4 {
-#if ADAM_NT
         typedef float v4 __attribute__((ext_vector_type(4)));
         const v4 r = __builtin_nontemporal_load(reinterpret_cast<const v4*>(q));
         return make_float4(r.x, r.y, r.z, r.w);
-#else
-        return *reinterpret_cast<const float4*>(q);
-#endif
     };
     auto st4 = [](float* q, const float4& x) {
-#if ADAM_NT
         typedef float v4 __attribute__((ext_vector_type(4)));
         v4 r = {x.x, x.y, x.z, x.w};
         __builtin_nontemporal_store(r, reinterpret_cast<v4*>(q));
-#else
-        *reinterpret_cast<float4*>(q) = x;
-#endif
     };
     const int sh = t.grad_shift;
     const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.m | (uintptr_t)t.v | (sh > 0 ? (uintptr_t)0 : (uintptr_t)t.g)) & 15) == 0) && (sh == 0 || sh >= 2);

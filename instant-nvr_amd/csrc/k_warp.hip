@@ -10,7 +10,6 @@
 // One thread per pair.  The 24 joint matrices and the deformer MLP weights are wave-uniform:
 // they are read through the scalar path (s_load) and used as SGPR operands of v_fmac.
 // The deformer tables are 0.34 MB (L2 resident).
-#include <stdlib.h>
 #include "pipeline.h"
 #include "grid_generic.h"
 #include "front_bodies.h"
@@ -252,7 +251,7 @@ __device__ __forceinline__ void lane_level_f2(const GridDev& dg, const LaneLevel
     }
 }
 
-template <int DF_CB>                    // 16-pair tiles in flight per wave (register budget)
+#define DF_CB 2                         // 16-pair tiles in flight per wave (register budget)
 __global__ __launch_bounds__(DF_BLOCK) void k_deform_pairs(RenderArgs a, Workspace w, GridDev dg,
                                                            const float* __restrict__ W0, const float* __restrict__ B0,
                                                            const float* __restrict__ W1, const float* __restrict__ B1,
@@ -425,10 +424,8 @@ __device__ __forceinline__ void lane_level_slice(const float2* S, const LaneSlic
 // scaled.  {min, exp2, add, log2} = 4 instructions per value instead of the 7 of softplus_f; 64 values per pair.
 __device__ __forceinline__ float softplus_log2(float a) { return log2_raw(1.0f + exp2_raw(fminf(a, 126.0f))); }
 
-#ifndef DF_WPE
 #define DF_WPE 3
-#endif
-template <int DF_CB, bool VSMALL>        // VSMALL: the UV volume qualifies for 24-bit index math (volume_is_small, common.h)
+template <bool VSMALL>        // VSMALL: the UV volume qualifies for 24-bit index math (volume_is_small, common.h)
 __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(DF_WPE, DF_WPE))) void k_deform_pairs_slice(RenderArgs a, Workspace w, GridDev dg, DfSliceInfo si,
                                                                  const float* __restrict__ W0, const float* __restrict__ B0,
                                                                  const float* __restrict__ W1, const float* __restrict__ B1,
@@ -558,7 +555,7 @@ __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(DF_WPE
 // depends on the grid and frame_dim only (not on the pair lists): launched on the side stream beside the KNN
 int launch_deform_slice(const RenderArgs& a, const Workspace& w, const GridDev& dg, hipStream_t st) {
     DfSliceInfo si;
-    if (!deform_slices_fit(dg, si, deform_cb())) return 0;
+    if (!deform_slices_fit(dg, si)) return 0;
     hipLaunchKernelGGL(k_deform_slice, dim3((unsigned)cdiv(si.off[8], 256)), dim3(256), 0, st, dg, si, a.scene.frame_dim, w.dslice);
     INVR_LAUNCH_CHECK();
     return 0;
@@ -573,6 +570,7 @@ int launch_deform_slice(const RenderArgs& a, const Workspace& w, const GridDev& 
 // 125 us with one workgroup per CU — bound by the LDS atomics of the coarse levels (all points of a workgroup on 16..50 entries;
 // reducing wave-uniform cells with shuffles first did not help: the UV coordinates of neighbouring points are unrelated).
 #define DSB_BLOCK 1024
+#define DSB_GRID 256            // workgroups at most: one per CU
 __global__ __launch_bounds__(DSB_BLOCK) void k_deform_slice_bwd(GridDev dg, DfSliceInfo si, const float* __restrict__ frame_dim,
                                                                 const float* __restrict__ uvt, const float* __restrict__ gfeat,
                                                                 int64_t n_host, const int32_t* __restrict__ count, int feat_dim,
@@ -640,12 +638,11 @@ __global__ __launch_bounds__(DSB_BLOCK) void k_deform_slice_bwd(GridDev dg, DfSl
 int launch_deform_slice_bwd(const GridDev& dg, const float* frame_dim, const float* uvt, const float* gfeat, int64_t n_max,
                             const int32_t* count, float* g_dense, float* g_hash, hipStream_t st) {
     DfSliceInfo si;
-    if (!deform_slices_fit(dg, si, deform_cb()) || dg.F != 2 || dg.sum || !dg.include_input) return -1;
+    if (!deform_slices_fit(dg, si) || dg.F != 2 || dg.sum || !dg.include_input) return -1;
     if (n_max == 0) return 0;
     const size_t lds_bytes = (size_t)si.off[8] * sizeof(float2);
     const int64_t tiles = cdiv(n_max, DSB_BLOCK);
-    static const int gmax = getenv("INVR_DSB_GRID") ? atoi(getenv("INVR_DSB_GRID")) : 256;
-    const unsigned grid = (unsigned)(tiles < gmax ? (tiles > 0 ? tiles : 1) : gmax);
+    const unsigned grid = (unsigned)(tiles < DSB_GRID ? (tiles > 0 ? tiles : 1) : DSB_GRID);
     hipLaunchKernelGGL(k_deform_slice_bwd, dim3(grid), dim3(DSB_BLOCK), lds_bytes, st, dg, si, frame_dim, uvt, gfeat, n_max, count,
                        3 + 16, g_dense, g_hash);
     INVR_LAUNCH_CHECK();
@@ -659,24 +656,17 @@ int launch_warp_pairs(const RenderArgs& a, const Workspace& w, const GridDev& dg
     INVR_LAUNCH_CHECK();
     int64_t dtiles = cdiv(w.lcap, DF_BLOCK);
     unsigned dgx = (unsigned)(dtiles < 512 ? (dtiles > 0 ? dtiles : 1) : 512);
-    const int cbv = deform_cb();
     DfSliceInfo si;
-    if (deform_slices_fit(dg, si, cbv)) {                 // slices built by launch_deform_slice
+    if (deform_slices_fit(dg, si)) {                 // slices built by launch_deform_slice
         const size_t lds_bytes = (size_t)DF_LDS * sizeof(float) + (size_t)si.off[8] * sizeof(float2);
-        const bool vs = volume_is_small(a.scene.tuv);
-        auto kern = cbv == 1 ? (vs ? k_deform_pairs_slice<1, true> : k_deform_pairs_slice<1, false>)
-                             : (vs ? k_deform_pairs_slice<2, true> : k_deform_pairs_slice<2, false>);
+        auto kern = volume_is_small(a.scene.tuv) ? k_deform_pairs_slice<true> : k_deform_pairs_slice<false>;
         hipLaunchKernelGGL(kern, dim3(dgx, INVR_NUM_PARTS), dim3(DF_BLOCK), lds_bytes, st, a, w, dg, si, dm.w[0], dm.b[0],
                            dm.w[1], dm.b[1], dm.w[2], dm.b[2]);
         INVR_LAUNCH_CHECK();
         return 0;
     }
-    if (cbv % 10 == 1)
-        hipLaunchKernelGGL(k_deform_pairs<1>, dim3(dgx, INVR_NUM_PARTS), dim3(DF_BLOCK), 0, st, a, w, dg, dm.w[0], dm.b[0], dm.w[1],
-                           dm.b[1], dm.w[2], dm.b[2]);
-    else
-        hipLaunchKernelGGL(k_deform_pairs<2>, dim3(dgx, INVR_NUM_PARTS), dim3(DF_BLOCK), 0, st, a, w, dg, dm.w[0], dm.b[0], dm.w[1],
-                           dm.b[1], dm.w[2], dm.b[2]);
+    hipLaunchKernelGGL(k_deform_pairs, dim3(dgx, INVR_NUM_PARTS), dim3(DF_BLOCK), 0, st, a, w, dg, dm.w[0], dm.b[0], dm.w[1],
+                       dm.b[1], dm.w[2], dm.b[2]);
     INVR_LAUNCH_CHECK();
     return 0;
 }

@@ -10,21 +10,18 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define HID 64
 #define EMB_STEPS 5              // 20 / 4
 #define RGB1_STEPS 18            // 72 / 4
-#define RGB1F_STEPS 16           // forward kernels: the 8 latent inputs are constant per call and folded into the bias (64 / 4)
 
 // The colour MLP's two 64-wide layers (70 -> 64 and 64 -> 64) in the FORWARD kernels run on the bf16 matrix pipe at fp32 accuracy:
 // weights and activations are split into three bf16 terms (hi + mid + lo = the fp32 value exactly: 3 x 8 significand bits), and the six
 // leading products hi hi, hi mid, mid hi, hi lo, lo hi, mid mid (the dropped ones are <= 2^-24 relative) run as v_mfma_f32_16x16x32_bf16
 // with fp32 accumulation: 48 MFMAs of 16 cycles per 16-pair tile and layer instead of 64 fp32 MFMAs of 32 cycles.  Measured on the
 // layer alone (tools/mlp_layer_microbench.hip, splitting and activation included): 0.58x the time, error against float64 7.4e-7 (fp32
-// MFMA: 8.7e-7).  -DMLP_BF16=0 builds the fp32 form (the A/B switch of profiles/r4_bf16_mlp.md).
-#ifndef MLP_BF16
-#define MLP_BF16 1
-#endif
+// MFMA: 8.7e-7; the A/B against the fp32 form: profiles/r4_bf16_mlp.md).  The backward kernels stay on the fp32 matrix pipe.
 typedef __bf16 mlp_bf16x8 __attribute__((ext_vector_type(8)));
 #define RGB_BF_FLOATS (3 * 4 * 2 * 64 * 4)           // [split 3][m-tile 4][k-block 2][lane 64] x 8 bf16 = 24 KB per layer
-#define RGB1_LDS (MLP_BF16 && RGB_BF_FLOATS > RGB1_STEPS * 4 * 64 ? RGB_BF_FLOATS : RGB1_STEPS * 4 * 64)
-#define RGB2_LDS (MLP_BF16 && RGB_BF_FLOATS > 16 * 4 * 64 ? RGB_BF_FLOATS : 16 * 4 * 64)
+#define RGB1_LDS RGB_BF_FLOATS                       // both also hold the smaller fp32 images of the backward kernels
+#define RGB2_LDS RGB_BF_FLOATS
+static_assert(RGB_BF_FLOATS >= RGB1_STEPS * 4 * 64 && RGB_BF_FLOATS >= 16 * 4 * 64, "the fp32 images fit the bf16 x 3 carve");
 
 // x = hi + mid + lo exactly (round-to-nearest conversions; the remainders are exact fp32 subtractions)
 __device__ __forceinline__ void bf16_split3(float x, __bf16& hi, __bf16& mid, __bf16& lo) {
@@ -95,7 +92,7 @@ __device__ void stage_weights(const PartMlpDev& pm, float* lds) {
             lds[O_W_OCC2 + (LOG2DOM ? ((s >> 2) * 64 + ln) * 4 + (s & 3) : t)] = W1[(1 + i) * HID + hid_col(s, g)] * s_out;
         }
     }
-    if ((WHAT & 2) && LOG2DOM && MLP_BF16) {
+    if ((WHAT & 2) && LOG2DOM) {
         // bf16 x 3 images: element j of (m-tile mo, k-block kb, lane (g, i)) = W[16 mo + i][column of k-slot (s = 8 kb + j, g)]
         mlp_bf16x8* w1 = reinterpret_cast<mlp_bf16x8*>(lds + O_W_RGB1);
         mlp_bf16x8* w2 = reinterpret_cast<mlp_bf16x8*>(lds + O_W_RGB2);
@@ -114,16 +111,16 @@ __device__ void stage_weights(const PartMlpDev& pm, float* lds) {
             dst[(1 * 8 + mo * 2 + kb) * 64 + ln] = vm;
             dst[(2 * 8 + mo * 2 + kb) * 64 + ln] = vl;
         }
-    } else if (WHAT & 2) {
-        for (int t = threadIdx.x; t < (LOG2DOM ? RGB1F_STEPS : RGB1_STEPS) * 4 * 64; t += MLP_BLOCK) {
+    } else if (WHAT & 2) {              // fp32 images (backward kernels)
+        for (int t = threadIdx.x; t < RGB1_STEPS * 4 * 64; t += MLP_BLOCK) {
             int ln = t & 63, mt = (t >> 6) & 3, s = t >> 8, g = ln >> 4, i = ln & 15;
-            int col = LOG2DOM ? rgb1f_col(s, g) : rgb1_col(s, g);
-            lds[O_W_RGB1 + (LOG2DOM ? (s * 64 + ln) * 4 + mt : t)] = col >= 0 ? R0[(16 * mt + i) * 70 + col] * s_in : 0.0f;
+            int col = rgb1_col(s, g);
+            lds[O_W_RGB1 + t] = col >= 0 ? R0[(16 * mt + i) * 70 + col] * s_in : 0.0f;
         }
         if (NRGB == 3)
             for (int t = threadIdx.x; t < 16 * 4 * 64; t += MLP_BLOCK) {
                 int ln = t & 63, mt = (t >> 6) & 3, s = t >> 8, g = ln >> 4, i = ln & 15;
-                lds[O_W_RGB2 + (LOG2DOM ? (s * 64 + ln) * 4 + mt : t)] = R1[(16 * mt + i) * HID + hid_col(s, g)];
+                lds[O_W_RGB2 + t] = R1[(16 * mt + i) * HID + hid_col(s, g)];
             }
     }
     for (int t = threadIdx.x; t < 64; t += MLP_BLOCK) {

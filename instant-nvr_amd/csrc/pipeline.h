@@ -155,7 +155,7 @@ int launch_deform_slice(const RenderArgs& a, const Workspace& w, const GridDev& 
 int launch_warp_pairs(const RenderArgs& a, const Workspace& w, const GridDev& dg, const MlpDev& dm, hipStream_t st);
 int launch_part_encode(const GridDev& g, const float* x_soa, int64_t stride, const int32_t* count, int64_t cap,
                        float* emb, hipStream_t st);
-struct EncodeAllArgs {            // k_part_encode_rs_all: the five part grids of one render
+struct EncodeAllArgs {            // k_part_encode_rs_xcd: the five part grids of one render
     GridDev g[INVR_NUM_PARTS];
     const float* xs[INVR_NUM_PARTS];
     float* emb[INVR_NUM_PARTS];

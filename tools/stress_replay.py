@@ -16,7 +16,6 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-import ctypes as C_                  # noqa: E402
 import torch                         # noqa: E402
 
 import invr                          # noqa: E402,F401
@@ -92,20 +91,6 @@ def ws_diff(ws_now, ws_good, wsinfo, stats):
                         ent = ne.nonzero()[:, 0]
                     d['entries'] = ent[:48].tolist()
                     d['n_entries'] = int(ent.numel())
-                    if name in ('l_x', 'l_d') and hasattr(_abi.lib(), 'invr_debug_warp_dump_offset') and ent.numel():
-                        # -DWARP_DUMP build: k_warp_pairs left its intermediates [part][36][lcap] in the last array of the workspace:
-                        # rows 0-11 A_bw, 12-23 B_bw, 24-26 pose point, 27-29 pose direction, 30-32 x_b, 33-35 d_b
-                        L_ = _abi.lib()
-                        L_.invr_workspace_bytes.restype = C_.c_size_t
-                        tot = int(L_.invr_workspace_bytes(C_.c_int64(n), C_.c_int32(S), C_.c_int64(cap)))
-                        lc = vn['lcap']
-                        size = lc * 5 * 36 * 4
-                        off = (tot - size) // 256 * 256
-                        dn = ws_now[off:off + size].view(torch.float32).view(5, 36, lc)[p][:, ent[:16]]
-                        dg = ws_good[off:off + size].view(torch.float32).view(5, 36, lc)[p][:, ent[:16]]
-                        rows = (dn.view(torch.int32) != dg.view(torch.int32)).any(1).nonzero()[:, 0].tolist()
-                        d['intermediates_differing_rows'] = rows
-                        d['intermediates'] = {str(r): {'now': dn[r][:6].tolist(), 'good': dg[r][:6].tolist()} for r in rows[:12]}
                     if name in ('l_x', 'l_d') and ent.numel():
                         e = ent[:16]
                         d['dump'] = {'l_x_now': vn['l_x'][p][:, e].tolist(), 'l_x_good': vg['l_x'][p][:, e].tolist(),
@@ -151,28 +136,6 @@ def main():
         _, batches = bench.frame_batches(512, 1.8, K, dev)
     refs = refs_of(net, batches, S, 0, world)
     bad, first, checked = 0, None, 0
-    import ctypes as C
-    L = _abi.lib()
-    have_dbg = hasattr(L, 'invr_debug_warp')           # the -DWARP_VERIFY variant (INVR_LIB_PATH=variants/libinvr_verify.so)
-    dbg_events = []
-
-    def read_dbg(rep):
-        if not have_dbg:
-            return
-        buf = (C.c_ulonglong * (8 + 64 * 8))()
-        L.invr_debug_warp(buf, 1)
-        if buf[1]:
-            recs = []
-            for n in range(min(int(buf[1]), 64)):
-                r = buf[8 + n * 8: 16 + n * 8]
-                import struct
-                f = lambda b: struct.unpack('f', struct.pack('I', b & 0xFFFFFFFF))[0]
-                recs.append({'p': r[0], 'i': r[1], 'lane': r[1] % 64, 'c': r[2] & 255, 'arr': ('l_x', 'l_d', 'reload of vmat row (c = neighbour * 6 + row; got = first load, expect = second)', 'blend FMAs twice (got = first, expect = second)', 'pose point twice', 'warp_with_mats twice', 'slot / nn / weights loaded twice')[min(int(r[2] >> 8), 6)], 'got': f(r[3]), 'expect': f(r[4]),
-                             'hw_id': hex(r[5]), 'xcc': r[6] & 15, 'block': r[7]})
-            dbg_events.append({'replay': rep, 'verify_launches': int(buf[0]), 'differing': int(buf[1]), 'records': recs})
-            sys.stderr.write('VERIFY replay %d: %d differing values right behind k_warp_pairs: %s\n' % (rep, buf[1], json.dumps(recs[:20])))
-    if have_dbg:
-        L.invr_debug_warp(None, 1)
 
     def compare(get, rep, wsinfo=None):
         nonlocal bad, first
@@ -210,7 +173,6 @@ def main():
                 continue
             torch.cuda.synchronize()
             checked += 1
-            read_dbg(rep)
             assert iframes.check_overflow(fs)
 
             def wsinfo(k):
@@ -249,9 +211,8 @@ def main():
             o, kk, rr = q.popleft()
             check_one(o, kk, rr)
         r.flush(release=True)
-        read_dbg(-1)
     print(json.dumps({'config': args.config, 'mode': args.mode, 'frames_in_flight': K if args.mode != 'lanes' else 8, 'replays': args.replays,
-                      'checked': checked, 'mismatching': bad, 'first': first, 'verify_events': dbg_events[:20]}))
+                      'checked': checked, 'mismatching': bad, 'first': first}))
     return 1 if bad else 0
 
 
