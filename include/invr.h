@@ -155,6 +155,27 @@ int invr_render_fwd(const InvrScene* scene, const InvrModel* model,
                     float* z_vals, int32_t* stats,
                     void* workspace, size_t workspace_bytes, int64_t max_active, void* stream);
 
+/* invr_render_fwd into a caller-owned raw buffer whose zero rows are TRACKED instead of rewritten.  93 % of the rows of an eval frame's
+ * raw are the zeros of ray-samples the cull dropped (the reference's scatter into a zero tensor, inb_part_network_multiassign.py:
+ * 156-159): a caller that renders frame after frame into one buffer gets them from the frame before.
+ *   raw       : raw_rows >= n_rays * n_samples rows of 16 bytes (16-byte aligned)
+ *   raw_dirty : one bit per row, invr_raw_dirty_bytes(raw_rows) = 8 * ceil(raw_rows / 64) bytes: row r = bit r & 63 of word r >> 6
+ * Contract.  On entry every row whose bit is clear holds four +0.0f; on exit the same holds, the first N = n_rays * n_samples rows are
+ * bit for bit what invr_render_fwd would have written, and the rows and bits at or beyond N are untouched.  A caller starts a pair
+ * either by zeroing both buffers or by leaving raw uninitialised and setting every dirty bit.  The dirty state is the caller's on
+ * purpose: a header inside the buffer could survive a free and a reallocation at the same address, and the library does not guess.
+ * A set bit only says "may be non-zero": the rows of survivors beyond max_active (zeros, stats[INVR_STAT_OVERFLOW]) count as dirty.
+ * With n_samples a multiple of 64 only the rows that are dirty now or were dirty on entry are stored; other sample counts store
+ * densely and update the bits.  occ and weights must be NULL (occ is raw's fourth channel); every other argument as invr_render_fwd. */
+size_t invr_raw_dirty_bytes(int64_t rows);
+int invr_render_fwd_tracked(const InvrScene* scene, const InvrModel* model,
+                            const float* ray_o, const float* ray_d, const float* near, const float* far,
+                            const float* jitter, int64_t n_rays, int32_t n_samples,
+                            float* rgb_map, float* acc_map, float* raw, float* occ, float* weights,
+                            float* z_vals, int32_t* stats,
+                            void* workspace, size_t workspace_bytes, int64_t max_active, void* stream,
+                            uint64_t* raw_dirty, int64_t raw_rows);
+
 /* The gradient-free front half of invr_render_fwd only (sampling, cull, KNN skinning, LBS warp,
  * deformer): fills the pair lists / flags / counters in the workspace (invr_workspace_layout) and
  * z_vals (n_rays,n_samples) (optional).  Used by the training forward, which recomputes the

@@ -94,7 +94,8 @@ EXPORTS = ['invr_last_error', 'invr_version', 'invr_sizeof', 'invr_workspace_byt
            'invr_knn_neighbors', 'invr_pose_points', 'invr_adam_advance', 'invr_train_workspace_bytes', 'invr_train_fwd',
            'invr_train_bwd', 'invr_expand_row_grad', 'invr_train_loss_fwd', 'invr_train_loss_bwd',
            'invr_part_encode_workspace', 'invr_part_encode_fwd', 'invr_part_encode_bwd_lists',
-           'invr_eval_workspace_bytes', 'invr_image_assemble', 'invr_image_metrics']
+           'invr_eval_workspace_bytes', 'invr_image_assemble', 'invr_image_metrics',
+           'invr_raw_dirty_bytes', 'invr_render_fwd_tracked']
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
 BWD_HEAD, BWD_DEFORMER, BWD_ALL = 1, 64, 127
 EVAL_RESULT_BYTES = 64   # include/invr.h INVR_EVAL_RESULT_BYTES: float64[3] (SSE, sum gt, sum S), int32[8] (windows, x, y, w, h, status, set, 0)
@@ -129,6 +130,10 @@ def lib():
         vp = C.c_void_p
         L.invr_render_fwd.argtypes = [C.POINTER(InvrScene), C.POINTER(InvrModel), vp, vp, vp, vp, vp, C.c_int64,
                                       C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int64, vp]
+        L.invr_render_fwd_tracked.argtypes = L.invr_render_fwd.argtypes + [vp, C.c_int64]
+        L.invr_render_fwd_tracked.restype = C.c_int
+        L.invr_raw_dirty_bytes.restype = C.c_size_t
+        L.invr_raw_dirty_bytes.argtypes = [C.c_int64]
         L.invr_grid_encode_fwd.argtypes = [C.POINTER(InvrGrid), vp, C.c_int64, vp, vp]
         L.invr_sample_volume.argtypes = [vp, C.c_int32 * 3, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp, vp]
         L.invr_knn_blend.argtypes = [C.POINTER(InvrScene), vp, C.c_int64, vp, vp, vp]

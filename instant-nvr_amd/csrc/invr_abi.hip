@@ -335,7 +335,7 @@ static int render_impl(const InvrScene* scene, const InvrModel* model,
                        float* rgb_map, float* acc_map, float* raw, float* occ, float* weights,
                        float* z_vals, int32_t* stats,
                        void* workspace, size_t workspace_bytes, int64_t max_active, void* stream,
-                       bool geometry_only = false, bool may_reorder = false) {
+                       bool geometry_only = false, bool may_reorder = false, uint64_t* raw_dirty = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     INVR_CHECK(scene && model, "invr_render_fwd: null scene/model");
     INVR_CHECK(n_rays >= 0 && (n_samples >= 2 || (wpts && n_samples == 1)), "invr_render_fwd: need n_rays >= 0 and n_samples >= 2");
@@ -431,7 +431,7 @@ static int render_impl(const InvrScene* scene, const InvrModel* model,
     }
     if (!geometry_only) {
         ProfStage ps(INVR_STAGE_COMPOSITE, st);
-        if (launch_merge_composite(a, w, rgb_map, acc_map, raw, occ, weights, st)) return 1;
+        if (launch_merge_composite(a, w, rgb_map, acc_map, raw, occ, weights, st, reinterpret_cast<unsigned long long*>(raw_dirty))) return 1;
     }
     if (g_prof_on) ++g_prof_renders;
     return 0;                   // (stats were exported by the KNN stage: the counters are final once the pair lists are)
@@ -445,6 +445,24 @@ extern "C" int invr_render_fwd(const InvrScene* scene, const InvrModel* model,
                                void* workspace, size_t workspace_bytes, int64_t max_active, void* stream) {
     return render_impl(scene, model, ray_o, ray_d, near, far, jitter, nullptr, nullptr, n_rays, n_samples, rgb_map, acc_map,
                        raw, occ, weights, z_vals, stats, workspace, workspace_bytes, max_active, stream, false, true);
+}
+
+extern "C" size_t invr_raw_dirty_bytes(int64_t rows) { return rows > 0 ? (size_t)cdiv(rows, 64) * sizeof(uint64_t) : 0; }
+
+extern "C" int invr_render_fwd_tracked(const InvrScene* scene, const InvrModel* model,
+                                       const float* ray_o, const float* ray_d, const float* near, const float* far,
+                                       const float* jitter, int64_t n_rays, int32_t n_samples,
+                                       float* rgb_map, float* acc_map, float* raw, float* occ, float* weights,
+                                       float* z_vals, int32_t* stats,
+                                       void* workspace, size_t workspace_bytes, int64_t max_active, void* stream,
+                                       uint64_t* raw_dirty, int64_t raw_rows) {
+    INVR_CHECK(raw && raw_dirty, "invr_render_fwd_tracked: null raw / raw_dirty");
+    INVR_CHECK(!occ && !weights, "invr_render_fwd_tracked: occ and weights must be NULL (occ is raw's fourth channel; the weights belong to the training calls)");
+    INVR_CHECK(n_rays >= 0 && n_samples >= 1 && raw_rows >= n_rays * (int64_t)n_samples, "invr_render_fwd_tracked: raw_rows %lld < n_rays * n_samples",
+               (long long)raw_rows);
+    INVR_CHECK(((uintptr_t)raw & 15) == 0 && ((uintptr_t)raw_dirty & 7) == 0, "invr_render_fwd_tracked: raw must be 16-byte, raw_dirty 8-byte aligned");
+    return render_impl(scene, model, ray_o, ray_d, near, far, jitter, nullptr, nullptr, n_rays, n_samples, rgb_map, acc_map,
+                       raw, nullptr, nullptr, z_vals, stats, workspace, workspace_bytes, max_active, stream, false, true, raw_dirty);
 }
 
 extern "C" int invr_geometry_fwd(const InvrScene* scene, const InvrModel* model,

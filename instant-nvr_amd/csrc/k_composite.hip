@@ -3,7 +3,8 @@
 // the scatter into full-size raw/occ (:156-159) and volume_rendering / render_weights
 // (lib/utils/net_utils.py:12-44 as called at inb_renderer.py:72, i.e. epsilon = 0, no background).
 //
-// One wave per ray, lane = sample (64 samples per pass): transmittance is an exclusive product
+// Lane = sample, 64 samples per pass, a wave walks the passes of a ray (k_composite: one wave per ray; k_composite_words, the merged
+// source with S a multiple of 64: one wave per CMP_GROUP rays, live passes only): transmittance is an exclusive product
 // scan done with 6 wave shuffles, rgb/acc are wave reductions.  The merge is done on the fly from
 // the per-(slot,part) results, so the (N,4) raw tensor is only written when the caller wants it.
 #include "pipeline.h"
@@ -49,8 +50,8 @@ struct MergedRaw {     // merge per-part results of the survivor slot of sample 
     const uint8_t* wsel;                 // the merge's choice per survivor (k_winner_lists)
     const float4* rgbw;                  // [rgb, occ] of the winning listed pair at the survivor's slot; far constants at [lcap + p]
     int64_t const_slot;
-    __device__ __forceinline__ float4 get(int64_t i) const {
-        const unsigned long long m = mask[i >> 6];
+    __device__ __forceinline__ float4 get(int64_t i) const { return get_m(i, mask[i >> 6]); }
+    __device__ __forceinline__ float4 get_m(int64_t i, unsigned long long m) const {          // m = mask[i >> 6]
         const int bit = (int)(i & 63);
         int slot = -1;
         if ((m >> bit) & 1ull) {
@@ -104,8 +105,132 @@ __global__ __launch_bounds__(CMP_BLOCK) void k_composite(Src src, int64_t R, int
     }
 }
 
-// (one workgroup per four rays: a fixed grid of 4096 workgroups walking the rays measured the same 135 us — the kernel is bound by
-// its 16 B / sample of output, not by dispatch)
+// The merged source when S is a multiple of 64: every 64-sample pass of a ray is exactly one aligned word of the survivor mask, owned
+// by one wave alone, so the wave reads the word once, as a wave-uniform value, and decides per pass what the pass needs.
+//  * A pass without a survivor (and epsilon 0) contributes nothing: its factors are 1 - 0 + 0 = 1 exactly, fmaf(0, 0, acc) and
+//    acc + 0 are exact, so the look-ups, the scan and the accumulation are skipped and the results keep their bits.  A ray without any
+//    survivor gets its zero map entries and nothing else.  (With epsilon != 0 — cfg.random_bg — an empty pass is not the identity: computed.)
+//  * TRACKED (invr_render_fwd_tracked): `dirty` holds one bit per row of the caller's raw buffer, clear = the row holds four +0.0f.  93 %
+//    of a frame's rows are zeros the cull dropped, the same zeros the frame before stored: only the rows of `cur | prev` are stored (zeros
+//    where only `prev` is set) and lane 0 brings the dirty word to `cur`.  The dirty word of a pass is as aligned and as private as its
+//    mask word.  Survivors beyond max_active (zero value, mask bit set) count as dirty.
+//  * One wave takes CMP_GROUP consecutive rays (while their words fit its 64 lanes): lane j fetches the mask and dirty words of the group's
+//    j-th pass in one load each, a ballot says which passes need anything at all, and the wave walks only those, in order, carrying the
+//    ray's transmittance and sums from pass to pass and writing the maps when the ray changes.  Most of a frame's rays
+//    have no survivor, and a wave of their own each cost them a launch and the latency of a first load: with no raw to store at all
+//    one wave per ray took 66 us at 512 x 512 x 128, eight rays per wave take 43 (4: 40, 16: 52, 32: 89 — the live passes of a wave
+//    are walked one after the other, each behind its own chain of look-ups; profiles/composite_tracked_raw.md).
+#define CMP_GROUP 8
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long x, int l) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), l);
+    return ((unsigned long long)hi << 32) | lo;
+}
+static int composite_group(int S) { const int npass = S >> 6; return npass >= 64 ? 1 : (64 / npass < CMP_GROUP ? 64 / npass : CMP_GROUP); }       // rays per wave
+
+template <bool TRACKED>
+__global__ __launch_bounds__(CMP_BLOCK) void k_composite_words(MergedRaw src, int64_t R, int S, int G, float eps, float* __restrict__ weights,
+                                                               float* __restrict__ rgb_map, float* __restrict__ acc_map,
+                                                               float4* __restrict__ raw_out, float* __restrict__ occ_out,
+                                                               unsigned long long* __restrict__ dirty) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r0 = ((int64_t)blockIdx.x * (CMP_BLOCK / 64) + (threadIdx.x >> 6)) * G;          // the wave's rays: [r0, r0 + nr)
+    if (r0 >= R) return;
+    const int npass = S >> 6;
+    const int nr = (int)min((int64_t)G, R - r0);
+    const int64_t w0 = r0 * npass;                        // ... and their words: [w0, w0 + nw)
+    const int nw = nr * npass;
+    const bool skip_empty = eps == 0.0f;
+    // passes that are walked whatever their words say: an output that is written densely, or arithmetic that is not the identity
+    const bool every = !skip_empty || occ_out != nullptr || weights != nullptr || (!TRACKED && raw_out != nullptr);
+    const cmp_v4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    float T_run = 1.0f, ar = 0.f, ag = 0.f, ab = 0.f, aw = 0.f;
+    int cur_ray = -1;                                     // the ray (of the group) whose passes are being walked
+    bool any = false;                                     // ... has contributed something
+    unsigned long long seen = 0ull;                       // rays of the group whose maps are written
+    for (int c0 = 0; c0 < nw; c0 += 64) {
+        const bool valid = c0 + lane < nw;
+        unsigned long long mw = 0ull, dw = 0ull;
+        if (valid) {
+            mw = src.mask[w0 + c0 + lane];
+            if (TRACKED) dw = dirty[w0 + c0 + lane];
+        }
+        unsigned long long act = __ballot(valid && (every || (mw | dw) != 0ull));
+        while (act != 0ull) {
+            const int p = __ffsll((long long)act) - 1;
+            act &= act - 1ull;
+            const int g = (c0 + p) / npass;
+            if (g != cur_ray) {
+                if (cur_ray >= 0) {
+                    if (any) { ar = wave_sum(ar); ag = wave_sum(ag); ab = wave_sum(ab); aw = wave_sum(aw); }
+                    if (lane == 0) {
+                        const int64_t ray = r0 + cur_ray;
+                        rgb_map[ray * 3] = ar; rgb_map[ray * 3 + 1] = ag; rgb_map[ray * 3 + 2] = ab;
+                        acc_map[ray] = aw;
+                    }
+                    seen |= 1ull << cur_ray;
+                }
+                cur_ray = g; any = false;
+                T_run = 1.0f; ar = ag = ab = aw = 0.f;
+            }
+            const unsigned long long cur = readlane_u64(mw, p);
+            const unsigned long long prev = TRACKED ? readlane_u64(dw, p) : 0ull;
+            const unsigned long long st = TRACKED ? (cur | prev) : (raw_out ? ~0ull : 0ull);      // rows of this pass to store
+            const int64_t wi = w0 + c0 + p, row = wi * 64 + lane;
+            if (cur == 0ull && skip_empty) {
+                if ((st >> lane) & 1ull) __builtin_nontemporal_store(zero4, reinterpret_cast<cmp_v4*>(raw_out) + row);
+                if (occ_out) occ_out[row] = 0.0f;
+                if (weights) weights[row] = 0.0f;
+                if (TRACKED && prev != 0ull && lane == 0) dirty[wi] = 0ull;
+                continue;
+            }
+            any = true;
+            const float4 v = src.get_m(row, cur);
+            // raw is the frame's largest output and nothing on the device reads it again: stored nontemporal (see k_composite)
+            if ((st >> lane) & 1ull) __builtin_nontemporal_store((cmp_v4){v.x, v.y, v.z, v.w}, reinterpret_cast<cmp_v4*>(raw_out) + row);
+            if (occ_out) occ_out[row] = v.w;
+            if (TRACKED && cur != prev && lane == 0) dirty[wi] = cur;
+            const float alpha = v.w;
+            const float incl = wave_incl_prod(1.0f - alpha + eps, lane);
+            const float excl = dpp_f<0x138, 0xF>(1.0f, incl);
+            const float wgt = alpha * (T_run * excl);
+            if (weights) weights[row] = wgt;
+            ar = fmaf(wgt, v.x, ar); ag = fmaf(wgt, v.y, ag); ab = fmaf(wgt, v.z, ab); aw += wgt;
+            T_run *= __int_as_float(__builtin_amdgcn_readlane(__float_as_int(incl), 63));
+        }
+    }
+    if (cur_ray >= 0) {
+        if (any) { ar = wave_sum(ar); ag = wave_sum(ag); ab = wave_sum(ab); aw = wave_sum(aw); }
+        if (lane == 0) {
+            const int64_t ray = r0 + cur_ray;
+            rgb_map[ray * 3] = ar; rgb_map[ray * 3 + 1] = ag; rgb_map[ray * 3 + 2] = ab;
+            acc_map[ray] = aw;
+        }
+        seen |= 1ull << cur_ray;
+    }
+    if (lane < nr && !((seen >> lane) & 1ull)) {          // rays none of whose passes was walked: nothing survived on them
+        const int64_t ray = r0 + lane;
+        rgb_map[ray * 3] = 0.f; rgb_map[ray * 3 + 1] = 0.f; rgb_map[ray * 3 + 2] = 0.f;
+        acc_map[ray] = 0.f;
+    }
+}
+
+// S not a multiple of 64: mask words straddle rays (waves), the stores stay dense, and the dirty words of [0, N) follow the frame's mask
+// in a launch of their own; the bits at or beyond N in the last word are the caller's and stay.
+__global__ __launch_bounds__(256) void k_dirty_from_mask(const unsigned long long* __restrict__ mask, int64_t N, unsigned long long* __restrict__ dirty) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= ((N + 63) >> 6)) return;
+    unsigned long long m = mask[i];
+    const int64_t left = N - i * 64;
+    if (left < 64) {
+        const unsigned long long valid = (1ull << left) - 1ull;
+        m = (m & valid) | (dirty[i] & ~valid);
+    }
+    dirty[i] = m;
+}
+
+// (k_composite, dense stores: one workgroup per four rays; a fixed grid of 4096 workgroups walking the rays measured the same 135 us —
+// with 16 B / sample of output that kernel is bound by its store stream, not by dispatch.  k_composite_words, which stores a fourteenth
+// of that or nothing, is not: see its header)
 static unsigned composite_grid(int64_t n_rays) { return (unsigned)cdiv(n_rays, CMP_BLOCK / 64); }
 
 int launch_composite(const float* raw, int64_t n_rays, int S, float eps, float* weights, float* rgb_map, float* acc_map, hipStream_t st) {
@@ -118,12 +243,27 @@ int launch_composite(const float* raw, int64_t n_rays, int S, float eps, float* 
 }
 
 int launch_merge_composite(const RenderArgs& a, const Workspace& w, float* rgb_map, float* acc_map, float* raw,
-                           float* occ, float* weights, hipStream_t st) {
+                           float* occ, float* weights, hipStream_t st, unsigned long long* raw_dirty) {
     if (a.R == 0) return 0;
     MergedRaw src{w.mask, w.word_off, w.ord_rows > 0 ? w.byte_off : nullptr, w.wsel, w.rgbw, w.cap};
+    if ((a.S & 63) == 0) {
+        const int G = composite_group(a.S);
+        if (raw_dirty)
+            hipLaunchKernelGGL(k_composite_words<true>, dim3(composite_grid(cdiv(a.R, G))), dim3(CMP_BLOCK), 0, st,
+                               src, a.R, a.S, G, a.scene.comp_eps, weights, rgb_map, acc_map, reinterpret_cast<float4*>(raw), occ, raw_dirty);
+        else
+            hipLaunchKernelGGL(k_composite_words<false>, dim3(composite_grid(cdiv(a.R, G))), dim3(CMP_BLOCK), 0, st,
+                               src, a.R, a.S, G, a.scene.comp_eps, weights, rgb_map, acc_map, reinterpret_cast<float4*>(raw), occ, (unsigned long long*)nullptr);
+        INVR_LAUNCH_CHECK();
+        return 0;
+    }
     hipLaunchKernelGGL(k_composite<MergedRaw>, dim3(composite_grid(a.R)), dim3(CMP_BLOCK), 0, st,
                        src, a.R, a.S, a.scene.comp_eps, weights, rgb_map, acc_map, reinterpret_cast<float4*>(raw), occ);
     INVR_LAUNCH_CHECK();
+    if (raw_dirty) {
+        hipLaunchKernelGGL(k_dirty_from_mask, dim3((unsigned)cdiv(cdiv(a.N, (int64_t)64), (int64_t)256)), dim3(256), 0, st, w.mask, a.N, raw_dirty);
+        INVR_LAUNCH_CHECK();
+    }
     return 0;
 }
 

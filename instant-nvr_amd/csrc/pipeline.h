@@ -197,4 +197,4 @@ struct MlpAllArgs {               // k_part_mlp_all
 // occ phase over every listed pair -> k_winner_lists -> rgb phase over the winners
 int launch_part_mlp_all(const MlpAllArgs& a, const Workspace& w, hipStream_t st);
 int launch_merge_composite(const RenderArgs& a, const Workspace& w, float* rgb_map, float* acc_map, float* raw,
-                           float* occ, float* weights, hipStream_t st);
+                           float* occ, float* weights, hipStream_t st, unsigned long long* raw_dirty = nullptr);     // raw_dirty: invr_render_fwd_tracked

@@ -173,7 +173,11 @@ class FrameSet:
 def shard_render_fns(net, batches, n_samples, rank, world, tile=DEFAULT_TILE, want_raw=True, cap_margin=1.3):
     """render_fns / n_rays for FrameSet from collated batches on the device: frame k's rays are dealt tile-cyclically, rank's shard is
     rendered by net.render_rays with a workspace of its own, sized from the survivor count of a first render (cap_margin x, as
-    Renderer does frame to frame; an overflow shows in stats[6] — check_overflow)."""
+    Renderer does frame to frame; an overflow shows in stats[6] — check_overflow).
+    With want_raw every frame also owns ONE raw buffer and its dirty words (invr_render_fwd_tracked), allocated next to its workspace:
+    the render that allocates the workspace, FrameSet's warm-up and every replay write into that pair, so a replay stores only the rows
+    that are non-zero now or were after the render before (93 % of a frame's rows are zeros the cull dropped).  `out['raw']` of every
+    call is a view of that buffer: library-owned memory, overwritten by the next replay, not to be written in place."""
     from .dist import tile_indices
     fns, n_rays, keep = [], [], []
     for b in batches:
@@ -186,13 +190,21 @@ def shard_render_fns(net, batches, n_samples, rank, world, tile=DEFAULT_TILE, wa
         st = net.render_rays(ctx, a[0], a[1], a[2], a[3], n_samples, want_raw=False)['stats'].cpu()
         cap = int(min(a[0].shape[0] * n_samples, max(65536, -(-int(float(st[0]) * cap_margin) // 65536) * 65536)))
         net._ws = None
-        net.render_rays(ctx, a[0], a[1], a[2], a[3], n_samples, want_raw=want_raw, max_active=cap)     # allocates this frame's workspace
+        # the frame's (raw, dirty) pair starts with raw uninitialised and every bit set.  The dirty words are device state that the
+        # renders carry forward: a graph capture records the kernels without running them, so the state the warm-up renders leave
+        # behind is the state the first replay sees, and every replay leaves the state the next one starts from.
+        pair = {}
+        if want_raw:
+            rows = a[0].shape[0] * n_samples
+            pair = {'raw_out': torch.empty(rows * 4, device=dev, dtype=torch.float32),
+                    'raw_dirty': torch.full((-(-rows // 64),), -1, device=dev, dtype=torch.int64)}
+        net.render_rays(ctx, a[0], a[1], a[2], a[3], n_samples, want_raw=want_raw, max_active=cap, **pair)     # allocates this frame's workspace
         ws = net._ws
         net._ws = None
 
-        def fn(ctx=ctx, a=a, ws=ws, cap=cap):
+        def fn(ctx=ctx, a=a, ws=ws, cap=cap, pair=pair):
             net._ws = ws
-            out = net.render_rays(ctx, a[0], a[1], a[2], a[3], n_samples, want_raw=want_raw, max_active=cap)
+            out = net.render_rays(ctx, a[0], a[1], a[2], a[3], n_samples, want_raw=want_raw, max_active=cap, **pair)
             net._ws = None
             return out
         fns.append(fn)

@@ -321,13 +321,17 @@ class Network(nn.Module):
         return out
 
     def render_rays(self, batch, ray_o, ray_d, near, far, n_samples, jitter=None, want_raw=True,
-                    want_weights=False, max_active=0, stream=None, raw_out=None):
+                    want_weights=False, max_active=0, stream=None, raw_out=None, raw_dirty=None):
         """One invr_render_fwd call over a ray list (n,3)/(n,).  `batch` is the collated batch dict
         or a RenderContext from prepare().  Returns a dict of device tensors.
         stream: launch on THAT torch stream instead of the current one while every tensor (outputs, workspace) still comes from the
         current stream's allocator pool (Renderer.in_flight lanes: K streams must not mean K private pools of 4 GB workspaces and
         0.5 GB raw tensors); the caller orders `stream` behind the current stream before the call, the tensors are recorded on it.
-        raw_out: a flat float32 device buffer of at least n * S * 4 elements to hold `raw` (a lane's buffer nobody references any more)."""
+        raw_out: a flat float32 device buffer of at least n * S * 4 elements to hold `raw` (a lane's buffer nobody references any more).
+        raw_dirty: with raw_out, the buffer's dirty words (int64, one bit per 16-byte row of ALL of raw_out, at least
+        ceil(rows / 64) of them): the call goes through invr_render_fwd_tracked, which stores only the rows that are non-zero now or
+        were on entry and keeps the words current (include/invr.h: a clear bit = the row holds zeros, on entry and on exit).  A new
+        pair starts zeroed, or with raw uninitialised and every word -1.  Not with want_weights."""
         L = _abi.lib()
         dev = ray_o.device
         ctx = batch if isinstance(batch, RenderContext) else self.prepare(batch)
@@ -348,14 +352,20 @@ class Network(nn.Module):
             jitter = f(jitter)
         nbytes = L.invr_workspace_bytes(n, S, max_active)
         ws = self.workspace(nbytes, dev)
-        _abi.check(L.invr_render_fwd(
-            C.byref(scene), C.byref(model), _abi.ptr(ray_o), _abi.ptr(ray_d), _abi.ptr(near), _abi.ptr(far),
-            _abi.ptr(jitter), n, S, _abi.ptr(out['rgb_map']), _abi.ptr(out['acc_map']),
-            _abi.ptr(out.get('raw')), _abi.ptr(None), _abi.ptr(out.get('weights')),
-            _abi.ptr(out.get('z_vals')), _abi.ptr(out['stats'], torch.int32),
-            C.c_void_p(ws.data_ptr()), nbytes, max_active, _abi.stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)))
+        args = (C.byref(scene), C.byref(model), _abi.ptr(ray_o), _abi.ptr(ray_d), _abi.ptr(near), _abi.ptr(far),
+                _abi.ptr(jitter), n, S, _abi.ptr(out['rgb_map']), _abi.ptr(out['acc_map']),
+                _abi.ptr(out.get('raw')), _abi.ptr(None), _abi.ptr(out.get('weights')),
+                _abi.ptr(out.get('z_vals')), _abi.ptr(out['stats'], torch.int32),
+                C.c_void_p(ws.data_ptr()), nbytes, max_active, _abi.stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream))
+        tracked = want_raw and raw_out is not None and raw_dirty is not None
+        if tracked:
+            rows = raw_out.numel() // 4
+            assert raw_out.dtype == torch.float32 and raw_out.is_contiguous() and raw_dirty.numel() * 64 >= rows, 'raw_dirty: one bit per row of raw_out'
+            _abi.check(L.invr_render_fwd_tracked(*args, _abi.ptr(raw_dirty, torch.int64), rows))
+        else:
+            _abi.check(L.invr_render_fwd(*args))
         if stream is not None:
-            for t in (ws, ray_o, ray_d, near, far, jitter) + tuple(v for v in out.values() if torch.is_tensor(v)):
+            for t in (ws, ray_o, ray_d, near, far, jitter, raw_dirty if tracked else None) + tuple(v for v in out.values() if torch.is_tensor(v)):
                 if t is not None:
                     t.record_stream(stream)
         if want_raw:

@@ -264,11 +264,16 @@ class _Lane:
         self.pending = None
         self.stats_host = None       # a page-locked copy target for the frame's statistics block (64 bytes, allocated once per lane)
         self.raw_buf = None          # the lane's `raw` buffer (0.5 GB for 512x512x128): handed to the next frame once nobody references it
+        self.raw_dirty = None        # its dirty words (invr_render_fwd_tracked): one bit per 16-byte row of raw_buf
 
     def raw_buffer(self, numel, device):
         """A flat float32 buffer of >= numel elements for this frame's raw: the lane's previous one when every dict / tensor that
         viewed it is gone (the common loop reads the maps and drops the dict: no 0.5 GB allocation per frame — hipMalloc of such
-        blocks took up to seconds when the caching allocator had to go back to the driver), else a fresh one."""
+        blocks took up to seconds when the caching allocator had to go back to the driver), else a fresh one.
+        The buffer comes with its dirty words, `self.raw_dirty` (one bit per row, all ones for a fresh buffer: its rows hold anything),
+        which the frames rendered into it keep current, so that a frame stores only the rows that are non-zero now or were before.
+        That makes the `raw` a lane returns library-owned memory: it is handed to a later frame once unreferenced, and whoever holds it
+        must not write it in place — a row zeroed or filled behind the library's back no longer matches its dirty bit."""
         buf = self.raw_buf
         if buf is not None and buf.numel() >= numel and buf.device == device:
             try:
@@ -278,6 +283,8 @@ class _Lane:
             if free:
                 return buf
         self.raw_buf = torch.empty(int(numel * 1.05) + 1024, device=device, dtype=torch.float32)
+        # (filled on the caller's stream: _PendingFrame._run takes the buffer BEFORE it orders the lane's stream behind the caller's)
+        self.raw_dirty = torch.full((-(-(self.raw_buf.numel() // 4) // 64),), -1, device=device, dtype=torch.int64)
         return self.raw_buf
 
     def stats_buffer(self, like):
@@ -302,10 +309,11 @@ class _PendingFrame:
         """the frame on the lane's stream; every device tensor comes from the CALLER's stream pool (Network.render_rays(stream=))"""
         r, lane, net = self.r, self.lane, self.r.net
         dev = lane.stream.device
+        raw_kw = r._lane_raw(lane, dev)                                  # (a fresh buffer's dirty words are filled on the caller's stream: before the wait)
         lane.stream.wait_stream(torch.cuda.current_stream(dev))          # inputs + freshly allocated blocks are ordered on the caller's stream
         prev, net._ws = net._ws, lane.ws
         try:
-            out = self.call(cap, lane.stream)
+            out = self.call(cap, lane.stream, raw_kw)
         finally:
             lane.ws, net._ws = net._ws, prev
         with torch.cuda.stream(lane.stream):
@@ -481,8 +489,8 @@ class Renderer:
             torch.cuda.empty_cache()
         self._raw_numel = max(getattr(self, '_raw_numel', 0), n_samp * 4)          # grow-only, renderer-wide: every lane's raw buffer fits the largest frame seen
         ctx = self.net.prepare(batch)          # on the caller's stream: a stale row-sum table is rebuilt in front of every lane
-        call = lambda c, st: self.net.render_rays(ctx, ray_o, ray_d, near, far, S, jitter=jitter, want_raw=self.want_raw, max_active=c, stream=st,
-                                                  raw_out=lane.raw_buffer(self._raw_numel, dev) if self.want_raw else None)
+        call = lambda c, st, raw_kw: self.net.render_rays(ctx, ray_o, ray_d, near, far, S, jitter=jitter, want_raw=self.want_raw, max_active=c,
+                                                          stream=st, **raw_kw)
         pend = _PendingFrame(self, lane, call, cap, (batch, ctx, ray_o, ray_d, near, far, jitter))
         pend.launch()
         lane.pending = pend
@@ -498,6 +506,12 @@ class Renderer:
         if self.eval_to_cpu:
             return self._track_lazy(LazyHostRet({}, {}, self.pin_host, pending=pend, keys=keys))
         return LazyDevRet(pend, keys)
+
+    def _lane_raw(self, lane, dev):
+        if not self.want_raw:
+            return {}
+        buf = lane.raw_buffer(self._raw_numel, dev)
+        return {'raw_out': buf, 'raw_dirty': lane.raw_dirty}
 
     def _track_lazy(self, ret):
         """bound the device memory behind returned LazyHostRet dicts (lazy_device_budget); called with every new dict"""
@@ -525,7 +539,7 @@ class Renderer:
             if lane.pending is not None:
                 lane.pending.result()
             if release:
-                lane.ws = lane.raw_buf = None
+                lane.ws = lane.raw_buf = lane.raw_dirty = None
 
     def _jitter(self, shape, device):
         return torch.rand(shape, device=device, dtype=torch.float32)
