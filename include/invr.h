@@ -473,6 +473,23 @@ int invr_expand_row_grad(const InvrGrid* grid, const float* row_grad, float* g_d
 int invr_part_encode_bwd_lists(const InvrGrid* grid, const float* x_soa, const float* g_out_soa, int64_t stride,
                                int64_t n_max, const int32_t* count, float* row_grad, float* g_x_soa, void* stream);
 
+/* The part-MLP backward and the weight-gradient reduction of one part in the forms invr_train_bwd runs them (stage entry points, as
+ * invr_part_encode_bwd_lists is for the encoder).
+ * invr_part_mlp_bwd_lists = invr_part_mlp_bwd on pair lists: SoA inputs / g_emb with `stride` floats between rows, the number of pairs
+ * read on the DEVICE (*count <= n_max <= stride, out->n_pad >= n_max; n_max only sizes the launch), the upstream gradient fetched as
+ * float4 g_raws[l_slot[pair] * 5 + pid] from the (cap,5) per-(slot, part) array of the merge backward — or g_raws[pair] of an (n,4)
+ * array when l_slot is NULL.  latent_full 1: out->g_latent is the whole (num_latent_code,8) gradient tensor and row *latent_index
+ * is accumulated into; 0: the 8 floats themselves.  Nothing at or past *count is read or written.
+ * invr_part_wgrad: gz (5,n_pad,64) and a (5,n_pad,72) as the backward left them -> ACCUMULATES (atomic float adds) dW[l] += gz[l]^T a[l],
+ * db[l] += column sums of gz[l] over rows [0, *count) (count DEVICE, *count <= n_pad), in the layers' own row-major weight
+ * layouts: dW[0] 64x19, dW[1] 17x64, dW[2] 64x70 (the k-slot order of a[2] undone), dW[3] 64x64 (n_rgb 3; ignored, may be NULL,
+ * for n_rgb 2), dW[4] 3x64; dW / db are HOST arrays of 5 DEVICE pointers. */
+int invr_part_mlp_bwd_lists(const InvrModel* model, int32_t pid, const int64_t* latent_index, const float* emb_soa,
+                            const float* dirs_soa, int64_t stride, int64_t n_max, const int32_t* count, const float* g_raws,
+                            const int32_t* l_slot, const InvrMlpBwdOut* out, int32_t latent_full, void* stream);
+int invr_part_wgrad(const float* gz, const float* a, int64_t n_pad, int32_t n_rgb, float* const* dW, float* const* db,
+                    const int32_t* count, void* stream);
+
 /* The training objective of NetworkWrapper.forward (lib/train/trainers/inb_trainer.py:40-98, 176-214 with the plain MSE image term,
  * use_lpips False) on the outputs of invr_train_fwd, one launch each way:
  *   loss = w_pair * pair + w_dist * mean(dist) + w_off * offset + mean((rgb_map - rgb_gt)^2)      (the wrapper's order of additions)

@@ -93,7 +93,7 @@ EXPORTS = ['invr_last_error', 'invr_version', 'invr_sizeof', 'invr_workspace_byt
            'invr_rigid_transformation', 'invr_pack_parts', 'invr_grid_row_sums_len', 'invr_grid_row_sums', 'invr_adam_chunk_elems', 'invr_adam_step', 'invr_part_mlp_fwd', 'invr_part_mlp_bwd',
            'invr_knn_neighbors', 'invr_pose_points', 'invr_adam_advance', 'invr_train_workspace_bytes', 'invr_train_fwd',
            'invr_train_bwd', 'invr_expand_row_grad', 'invr_train_loss_fwd', 'invr_train_loss_bwd',
-           'invr_part_encode_workspace', 'invr_part_encode_fwd', 'invr_part_encode_bwd_lists',
+           'invr_part_encode_workspace', 'invr_part_encode_fwd', 'invr_part_encode_bwd_lists', 'invr_part_mlp_bwd_lists', 'invr_part_wgrad',
            'invr_eval_workspace_bytes', 'invr_image_assemble', 'invr_image_metrics',
            'invr_raw_dirty_bytes', 'invr_render_fwd_tracked']
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
@@ -185,6 +185,11 @@ def lib():
         L.invr_part_mlp_fwd.restype = C.c_int
         L.invr_part_mlp_bwd.argtypes = [C.POINTER(InvrModel), C.c_int32, vp, vp, vp, C.c_int64, vp, C.POINTER(InvrMlpBwdOut), vp]
         L.invr_part_mlp_bwd.restype = C.c_int
+        L.invr_part_mlp_bwd_lists.argtypes = [C.POINTER(InvrModel), C.c_int32, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp,
+                                              C.POINTER(InvrMlpBwdOut), C.c_int32, vp]
+        L.invr_part_mlp_bwd_lists.restype = C.c_int
+        L.invr_part_wgrad.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(vp), C.POINTER(vp), vp, vp]
+        L.invr_part_wgrad.restype = C.c_int
         L.invr_adam_chunk_elems.restype = C.c_int32
         L.invr_adam_step.argtypes = [vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_float, vp]
         L.invr_adam_step.restype = C.c_int

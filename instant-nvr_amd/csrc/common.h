@@ -134,6 +134,16 @@ __device__ __forceinline__ float sigmoid_acc(float x) {
     const float e = exp2_raw(hi) * fmaf(lo, INVR_LN2, 1.0f);
     return (x >= 0.0f ? 1.0f : e) * __builtin_amdgcn_rcpf(1.0f + e);
 }
+// sigmoid'(x) = sigmoid(x) sigmoid(-x) = e / (1 + e)^2 with e = exp(-|x|) as in sigmoid_acc: relative accuracy for every x, where
+// s (1 - s) formed from a rounded s has none once |x| > ~8
+__device__ __forceinline__ float dsigmoid_acc(float x) {
+    const float ax = fabsf(x);
+    const float hi = -ax * INVR_LOG2E;
+    const float lo = fmaf(-ax, INVR_LOG2E, -hi) + -ax * 1.925963033500011e-8f;
+    const float e = exp2_raw(hi) * fmaf(lo, INVR_LN2, 1.0f);
+    const float r = __builtin_amdgcn_rcpf(1.0f + e);
+    return e * r * r;
+}
 
 // sin and cos of a moderate argument (|a| < ~100): Cody-Waite reduction to [-pi/4, pi/4] by
 // multiples of pi/2 (two-term constant, FMA), Cephes sinf/cosf minimax polynomials; |error| < 2e-7.

@@ -774,6 +774,36 @@ extern "C" int invr_part_mlp_bwd(const InvrModel* model, int32_t pid, const int6
     return launch_part_mlp_bwd(pm, emb_soa, dirs_soa, n, n, nullptr, g_raw, nullptr, pid, o, (hipStream_t)stream);
 }
 
+// The two kernels in the middle of a part's backward chain in the forms invr_train_bwd launches them (stage entry points: what
+// tests/test_gpu_mlp_bwd.py holds element by element to float64)
+extern "C" int invr_part_mlp_bwd_lists(const InvrModel* model, int32_t pid, const int64_t* latent_index, const float* emb_soa,
+                                       const float* dirs_soa, int64_t stride, int64_t n_max, const int32_t* count, const float* g_raws,
+                                       const int32_t* l_slot, const InvrMlpBwdOut* out, int32_t latent_full, void* stream) {
+    INVR_CHECK(model && latent_index && pid >= 0 && pid < INVR_NUM_PARTS && out && count, "invr_part_mlp_bwd_lists: bad model/pid/out/count");
+    INVR_CHECK(n_max >= 0 && n_max <= stride && n_max < (1ll << 31), "invr_part_mlp_bwd_lists: 0 <= n_max <= stride required");
+    if (n_max == 0) return 0;
+    PartMlpDev pm = make_part_mlp(model, pid, latent_index);
+    INVR_CHECK(emb_soa && dirs_soa && g_raws && out->g_emb && out->gz && out->a && out->g_latent && out->n_pad >= n_max,
+               "invr_part_mlp_bwd_lists: null pointer / n_pad < n_max");
+    const MlpDev& oc = pm.occ;
+    const MlpDev& r = pm.rgb;
+    INVR_CHECK(oc.n_linear == 2 && oc.dims[0] == 19 && oc.dims[1] == 64 && oc.dims[2] == 17 && (r.n_linear == 2 || r.n_linear == 3) &&
+               r.dims[0] == 70 && r.dims[1] == 64 && r.dims[r.n_linear] == 3 && pm.n_freq == 4 && pm.latent_dim == 8 && pm.geo_dim == 16,
+               "invr_part_mlp_bwd_lists: supports occ 19-64-17 and rgb 70-64(-64)-3");
+    MlpBwdOut o{out->g_emb, out->gz, out->a, out->n_pad, out->g_latent, latent_full ? 1 : 0};
+    return launch_part_mlp_bwd(pm, emb_soa, dirs_soa, n_max, stride, count, g_raws, l_slot, pid, o, (hipStream_t)stream);
+}
+
+extern "C" int invr_part_wgrad(const float* gz, const float* a, int64_t n_pad, int32_t n_rgb, float* const* dW, float* const* db,
+                               const int32_t* count, void* stream) {
+    INVR_CHECK(n_pad >= 0 && n_pad < (1ll << 31) && (n_rgb == 2 || n_rgb == 3), "invr_part_wgrad: bad n_pad / n_rgb");
+    if (n_pad == 0) return 0;
+    INVR_CHECK(gz && a && dW && db && count, "invr_part_wgrad: null pointer");
+    for (int l = 0; l < 5; ++l)
+        INVR_CHECK((l == 3 && n_rgb != 3) || (dW[l] && db[l]), "invr_part_wgrad: null gradient pointer (layer %d)", l);
+    return launch_part_wgrad(gz, a, n_pad, n_rgb, dW, db, count, (hipStream_t)stream);
+}
+
 // ---- training iteration (k_train.hip) ----------------------------------------------------------------------------------
 static size_t carve_train(TrainWs& t, void* base, size_t off0, int64_t N, int64_t lcap) {
     Carver c{(char*)base, off0};

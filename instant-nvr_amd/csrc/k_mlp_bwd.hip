@@ -39,10 +39,15 @@ extern "C" int invr_debug_mlpb_prof(unsigned long long* out, int reset) {
 #define MP_FLUSH
 #endif
 
-__device__ __forceinline__ f32x4 dsoftplus4(f32x4 gin, f32x4 act) {    // softplus'(z) = sigmoid(z) = 1 - exp(-softplus(z))
+// softplus'(z) = sigmoid(z), formed from the PRE-activation (sigmoid_acc: ~3 ulp relative for every z).  The kernel used to form it from
+// the activation, 1 - exp(-softplus(z)): a cancellation for z < 0 — 6e-8 ABSOLUTE on a factor ~e^z, i.e. 2e-5 of the factor at z = -6,
+// 4e-3 at z = -14, and exactly 0 below -17 — which is the whole weight-gradient row of a hidden unit that is off for every pair
+// (tests/test_gpu_mlp_bwd.py, the `wide` / `dead` weight sets; the deformer's backward made the same change, k_train.hip).  The three
+// hidden layers' pre-activations are kept in registers for it (48 VGPRs; the kernel runs one workgroup per CU).
+__device__ __forceinline__ f32x4 dsoftplus4(f32x4 gin, f32x4 z) {
     f32x4 r;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) r[k] = gin[k] * (1.0f - exp2_raw(-act[k] * INVR_LOG2E));
+    for (int k = 0; k < 4; ++k) r[k] = gin[k] * sigmoid_acc(z[k]);
     return r;
 }
 __device__ __forceinline__ void store4(float* p, f32x4 v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
@@ -96,11 +101,11 @@ __global__ __launch_bounds__(MLP_BLOCK, 1) void k_part_mlp_bwd(PartMlpDev pm, co
         for (int s = 0; s < EMB_STEPS; ++s)
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) h1[mt] = mfma4(lds[O_W_OCC1 + (s * 4 + mt) * 64 + lane], eb[s], h1[mt]);
+        f32x4 z1[4];
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) h1[mt] = softplus4(h1[mt]);
+        for (int mt = 0; mt < 4; ++mt) { z1[mt] = h1[mt]; h1[mt] = softplus4(h1[mt]); }
         f32x4 feat = bias4(lds + O_B_OCC2, 0, g);
         const float lg = head_dot(h1, lds + O_V_OCC, g) + lds[O_V_OCC + 64];
-        const float occ = one_minus_exp_neg(softplus_f(lg));
 #pragma unroll
         for (int s = 0; s < 16; ++s) feat = mfma4(lds[O_W_OCC2 + s * 64 + lane], h1[s >> 2][s & 3], feat);
         float kb[RGB1_STEPS];
@@ -132,8 +137,9 @@ __global__ __launch_bounds__(MLP_BLOCK, 1) void k_part_mlp_bwd(PartMlpDev pm, co
         for (int s = 0; s < RGB1_STEPS; ++s)
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) hr1[mt] = mfma4(lds[O_W_RGB1 + (s * 4 + mt) * 64 + lane], kb[s], hr1[mt]);
+        f32x4 zr1[4], zl[4];                                   // pre-activations: rgb layer 1, last hidden rgb layer
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) hr1[mt] = softplus4(hr1[mt]);
+        for (int mt = 0; mt < 4; ++mt) { zr1[mt] = hr1[mt]; hr1[mt] = softplus4(hr1[mt]); }
         f32x4 hl[4];                                           // last hidden rgb activation
         if (NRGB == 3) {
 #pragma unroll
@@ -143,20 +149,22 @@ __global__ __launch_bounds__(MLP_BLOCK, 1) void k_part_mlp_bwd(PartMlpDev pm, co
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt) hl[mt] = mfma4(lds[O_W_RGB2 + (s * 4 + mt) * 64 + lane], hr1[s >> 2][s & 3], hl[mt]);
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) hl[mt] = softplus4(hl[mt]);
+            for (int mt = 0; mt < 4; ++mt) { zl[mt] = hl[mt]; hl[mt] = softplus4(hl[mt]); }
         } else {
 #pragma unroll
-            for (int mt = 0; mt < 4; ++mt) hl[mt] = hr1[mt];
+            for (int mt = 0; mt < 4; ++mt) { zl[mt] = zr1[mt]; hl[mt] = hr1[mt]; }
         }
-        float rgb[3];
+        float zo[3];                                           // colour logits
 #pragma unroll
-        for (int c = 0; c < 3; ++c) rgb[c] = sigmoid_f(head_dot(hl, lds + O_V_OUT + c * 64, g) + lds[O_V_OUT + 3 * 64 + c]);
+        for (int c = 0; c < 3; ++c) zo[c] = head_dot(hl, lds + O_V_OUT + c * 64, g) + lds[O_V_OUT + 3 * 64 + c];
 
         MP(2)
         // ---------------- backward ----------------
         const float4 gr = live ? (l_slot ? g_raw[(int64_t)l_slot[pair] * INVR_NUM_PARTS + part] : g_raw[pair]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float go[3] = {gr.x * rgb[0] * (1.0f - rgb[0]), gr.y * rgb[1] * (1.0f - rgb[1]), gr.z * rgb[2] * (1.0f - rgb[2])};
-        const float g_lg = gr.w * (1.0f - occ) * occ;            // occ = 1 - exp(-softplus(lg)): d occ / d lg = (1 - occ) occ
+        // the heads' derivative factors from the logits as well: rgb (1 - rgb) and (1 - occ) occ lose the small one of their two
+        // factors to the rounding of the other (a logit of +-17 and beyond gave a gradient of exactly 0)
+        float go[3] = {gr.x * dsigmoid_acc(zo[0]), gr.y * dsigmoid_acc(zo[1]), gr.z * dsigmoid_acc(zo[2])};
+        const float g_lg = gr.w * dsigmoid_acc(lg);              // occ = 1 - exp(-softplus(lg)) = sigmoid(lg)
         // rgb head^T (VALU): g_hl[hid] = sum_c Wout[c][hid] go[c]
         f32x4 gz[4];
 #pragma unroll
@@ -168,7 +176,7 @@ __global__ __launch_bounds__(MLP_BLOCK, 1) void k_part_mlp_bwd(PartMlpDev pm, co
                 for (int c = 0; c < 3; ++c) a = fmaf(lds[O_V_OUT + c * 64 + g * 16 + mt * 4 + r], go[c], a);
                 gz[mt][r] = a;
             }
-            gz[mt] = dsoftplus4(gz[mt], hl[mt]);
+            gz[mt] = dsoftplus4(gz[mt], zl[mt]);
         }
         if (live) {
             if (g == 0) { G(4)[pair * 64] = go[0]; G(4)[pair * 64 + 1] = go[1]; G(4)[pair * 64 + 2] = go[2]; }
@@ -190,7 +198,7 @@ __global__ __launch_bounds__(MLP_BLOCK, 1) void k_part_mlp_bwd(PartMlpDev pm, co
                     for (int mi = 0; mi < 4; ++mi)
                         acc[mi] = mfma4(lds[O_W_RGB2 + ((4 * mi + (i & 3)) * 4 + mtp) * 64 + (i >> 2) * 16 + 4 * g + rp], gz[mtp][rp], acc[mi]);
 #pragma unroll
-            for (int mi = 0; mi < 4; ++mi) gz[mi] = dsoftplus4(acc[mi], hr1[mi]);
+            for (int mi = 0; mi < 4; ++mi) gz[mi] = dsoftplus4(acc[mi], zr1[mi]);
             if (live) {
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt) {
@@ -226,7 +234,7 @@ __global__ __launch_bounds__(MLP_BLOCK, 1) void k_part_mlp_bwd(PartMlpDev pm, co
 #pragma unroll
             for (int rp = 0; rp < 4; ++rp)
                 gh[mi] = mfma4(lds[O_W_OCC2 + (4 * mi + (i & 3)) * 64 + (i >> 2) * 16 + 4 * g + rp], gfeat[rp], gh[mi]);
-            gh[mi] = dsoftplus4(gh[mi], h1[mi]);
+            gh[mi] = dsoftplus4(gh[mi], z1[mi]);
         }
         if (live) {
             float* q = G(1) + pair * 64;
