@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('INVR_LIB_PATH') or os.path.join(HERE, 'libinvr.so')      # (INVR_LIB_PATH: experiment builds)
 
 MAX_LEVELS, MAX_LINEAR, STATS_LEN = 16, 4, 16
-_f32p, _i32p, _i64p, _u8p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+_f32p, _f64p, _i32p, _i64p, _u8p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
 
 
 class InvrGrid(C.Structure):
@@ -84,18 +84,70 @@ class InvrWsLayout(C.Structure):
                 ('byte_off', C.c_int64)]
 
 
-EXPORTS = ['invr_last_error', 'invr_version', 'invr_sizeof', 'invr_workspace_bytes', 'invr_render_fwd',
-           'invr_grid_encode_fwd', 'invr_sample_volume', 'invr_knn_blend', 'invr_warp_deform',
-           'invr_part_field_workspace', 'invr_part_field_fwd', 'invr_composite_fwd',
-           'invr_profile_enable', 'invr_profile_read', 'invr_workspace_layout', 'invr_deform_fwd',
-           'invr_distortion_fwd', 'invr_grid_encode_bwd', 'invr_composite_bwd',
-           'invr_field_workspace_bytes', 'invr_field_fwd', 'invr_geometry_fwd', 'invr_generate_rays',
-           'invr_rigid_transformation', 'invr_pack_parts', 'invr_grid_row_sums_len', 'invr_grid_row_sums', 'invr_adam_chunk_elems', 'invr_adam_step', 'invr_part_mlp_fwd', 'invr_part_mlp_bwd',
-           'invr_knn_neighbors', 'invr_pose_points', 'invr_adam_advance', 'invr_train_workspace_bytes', 'invr_train_fwd',
-           'invr_train_bwd', 'invr_expand_row_grad', 'invr_train_loss_fwd', 'invr_train_loss_bwd',
-           'invr_part_encode_workspace', 'invr_part_encode_fwd', 'invr_part_encode_bwd_lists', 'invr_part_mlp_bwd_lists', 'invr_part_wgrad',
-           'invr_eval_workspace_bytes', 'invr_image_assemble', 'invr_image_metrics',
-           'invr_raw_dirty_bytes', 'invr_render_fwd_tracked']
+def _signatures():
+    """name -> (restype, argtypes) of every prototype of include/invr.h, in the header's order (tests/test_abi_symbols.py holds each
+    entry against the header's text).  vp = any data pointer: device tensors, host arrays and the stream go through as addresses."""
+    i32, i64, f32, f64, size, vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_size_t, C.c_void_p
+    scene, model, grid = C.POINTER(InvrScene), C.POINTER(InvrModel), C.POINTER(InvrGrid)
+    rays = [vp, vp, vp, vp, vp, i64, i32]          # ray_o, ray_d, near, far, jitter, n_rays, n_samples
+    ws = [vp, size, i64, vp]                       # workspace, workspace_bytes, max_active, stream
+    render = [scene, model] + rays + [vp, vp, vp, vp, vp, vp, vp] + ws
+    return {
+        'invr_last_error': (C.c_char_p, ()),
+        'invr_version': (C.c_int, ()),
+        'invr_sizeof': (size, [i32]),
+        'invr_workspace_bytes': (size, [i64, i32, i64]),
+        'invr_render_fwd': (C.c_int, render),
+        'invr_raw_dirty_bytes': (size, [i64]),
+        'invr_render_fwd_tracked': (C.c_int, render + [vp, i64]),
+        'invr_geometry_fwd': (C.c_int, [scene, model] + rays + [vp, vp] + ws),
+        'invr_field_workspace_bytes': (size, [i64, i64]),
+        'invr_field_fwd': (C.c_int, [scene, model, vp, vp, i64, vp, vp, vp] + ws),
+        'invr_workspace_layout': (C.c_int, [i64, i32, i64, C.POINTER(InvrWsLayout)]),
+        'invr_profile_enable': (C.c_int, [i32]),
+        'invr_profile_read': (C.c_int, [_f32p, _i32p]),
+        'invr_grid_encode_fwd': (C.c_int, [grid, vp, i64, vp, vp]),
+        'invr_grid_encode_bwd': (C.c_int, [grid, vp, vp, i64, vp, vp, vp, vp]),
+        'invr_sample_volume': (C.c_int, [vp, i32 * 3, i32, i32, i32, vp, vp, i64, vp, vp]),
+        'invr_knn_blend': (C.c_int, [scene, vp, i64, vp, vp, vp]),
+        'invr_knn_neighbors': (C.c_int, [scene, vp, i64, vp, vp, vp, vp, vp]),
+        'invr_pose_points': (C.c_int, [scene] + rays + [vp, i64, vp, vp, vp]),
+        'invr_warp_deform': (C.c_int, [scene, model, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
+        'invr_part_field_workspace': (size, [i64]),
+        'invr_part_field_fwd': (C.c_int, [model, i32, vp, vp, vp, i64, vp, vp, size, vp]),
+        'invr_part_encode_workspace': (size, [i64]),
+        'invr_part_encode_fwd': (C.c_int, [grid, vp, i64, i32, vp, vp, size, vp]),
+        'invr_deform_fwd': (C.c_int, [scene, model, vp, i64, vp, vp]),
+        'invr_distortion_fwd': (C.c_int, [vp, vp, i64, i32, vp, vp]),
+        'invr_composite_fwd': (C.c_int, [vp, i64, i32, vp, vp, vp, vp]),
+        'invr_generate_rays': (C.c_int, [_f64p, _f64p, _f64p, _f64p, _f32p, i32, i32, vp, vp, vp, vp, vp]),
+        'invr_grid_row_sums_len': (i64, [vp]),
+        'invr_grid_row_sums': (C.c_int, [vp, vp, vp]),
+        'invr_part_mlp_fwd': (C.c_int, [model, i32, vp, vp, vp, i64, vp, vp, vp]),
+        'invr_part_mlp_bwd': (C.c_int, [model, i32, vp, vp, vp, i64, vp, C.POINTER(InvrMlpBwdOut), vp]),
+        'invr_adam_chunk_elems': (i32, ()),
+        'invr_adam_advance': (C.c_int, [vp, i32, f64, f64, vp]),
+        'invr_adam_step': (C.c_int, [vp, vp, vp, i64, f64, f64, f32, vp]),
+        'invr_rigid_transformation': (C.c_int, [vp, vp, vp, vp, vp]),
+        'invr_pack_parts': (C.c_int, [vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
+        'invr_train_workspace_bytes': (size, [i64, i32, i64]),
+        'invr_train_fwd': (C.c_int, [scene, model] + rays + [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp] + ws),
+        'invr_train_bwd': (C.c_int, [scene, model, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(InvrTrainGrads), i32] + ws),
+        'invr_expand_row_grad': (C.c_int, [grid, vp, vp, vp, vp]),
+        'invr_part_encode_bwd_lists': (C.c_int, [grid, vp, vp, i64, i64, vp, vp, vp, vp]),
+        'invr_part_mlp_bwd_lists': (C.c_int, [model, i32, vp, vp, vp, i64, i64, vp, vp, vp, C.POINTER(InvrMlpBwdOut), i32, vp]),
+        'invr_part_wgrad': (C.c_int, [vp, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), vp, vp]),
+        'invr_train_loss_fwd': (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, i32, vp, vp, vp]),
+        'invr_train_loss_bwd': (C.c_int, [vp, vp, vp, i64, f32, f32, f32, i32, vp, vp, vp, vp, vp]),
+        'invr_composite_bwd': (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp]),
+        'invr_eval_workspace_bytes': (size, [i32, i32]),
+        'invr_image_assemble': (C.c_int, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, size, vp]),
+        'invr_image_metrics': (C.c_int, [vp, vp, i32, i32, i32, vp, vp, size, vp]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTS = list(SIGNATURES)
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
 BWD_HEAD, BWD_DEFORMER, BWD_ALL = 1, 64, 127
 EVAL_RESULT_BYTES = 64   # include/invr.h INVR_EVAL_RESULT_BYTES: float64[3] (SSE, sum gt, sum S), int32[8] (windows, x, y, w, h, status, set, 0)
@@ -112,105 +164,16 @@ def lib():
             raise RuntimeError('libinvr.so is not built (%s); run `python -c "import __graft_entry__ as g; g.build()"`. '
                                'There is no CPU fallback for the render path.' % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        L.invr_last_error.restype = C.c_char_p
-        L.invr_version.restype = C.c_int
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, list(argtypes)
         if L.invr_version() != ABI_VERSION:
             raise RuntimeError('libinvr.so speaks ABI version %d, this binding %d (include/invr.h INVR_ABI_VERSION): rebuild the library '
                                '(python -m invr.build)' % (L.invr_version(), ABI_VERSION))
-        L.invr_sizeof.restype = C.c_size_t
-        L.invr_sizeof.argtypes = [C.c_int32]
         for i, t in enumerate((InvrGrid, InvrMlp, InvrPart, InvrModel, InvrScene, InvrWsLayout, InvrMlpBwdOut, InvrAdamTensor, InvrTrainGrads)):
             if L.invr_sizeof(i) != C.sizeof(t):
                 raise RuntimeError('libinvr ABI mismatch: struct %s is %d bytes in the library, %d in the binding'
                                    % (t.__name__, L.invr_sizeof(i), C.sizeof(t)))
-        L.invr_workspace_bytes.restype = C.c_size_t
-        L.invr_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64]
-        L.invr_part_field_workspace.restype = C.c_size_t
-        L.invr_part_field_workspace.argtypes = [C.c_int64]
-        vp = C.c_void_p
-        L.invr_render_fwd.argtypes = [C.POINTER(InvrScene), C.POINTER(InvrModel), vp, vp, vp, vp, vp, C.c_int64,
-                                      C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int64, vp]
-        L.invr_render_fwd_tracked.argtypes = L.invr_render_fwd.argtypes + [vp, C.c_int64]
-        L.invr_render_fwd_tracked.restype = C.c_int
-        L.invr_raw_dirty_bytes.restype = C.c_size_t
-        L.invr_raw_dirty_bytes.argtypes = [C.c_int64]
-        L.invr_grid_encode_fwd.argtypes = [C.POINTER(InvrGrid), vp, C.c_int64, vp, vp]
-        L.invr_sample_volume.argtypes = [vp, C.c_int32 * 3, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int64, vp, vp]
-        L.invr_knn_blend.argtypes = [C.POINTER(InvrScene), vp, C.c_int64, vp, vp, vp]
-        L.invr_adam_advance.argtypes = [vp, C.c_int32, C.c_double, C.c_double, vp]
-        L.invr_adam_advance.restype = C.c_int
-        L.invr_train_workspace_bytes.restype = C.c_size_t
-        L.invr_train_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int64]
-        L.invr_train_fwd.argtypes = [C.POINTER(InvrScene), C.POINTER(InvrModel), vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, C.c_int64,
-                                     vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, C.c_int64, vp]
-        L.invr_train_fwd.restype = C.c_int
-        L.invr_train_bwd.argtypes = [C.POINTER(InvrScene), C.POINTER(InvrModel), C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                     C.POINTER(InvrTrainGrads), C.c_int32, vp, C.c_size_t, C.c_int64, vp]
-        L.invr_train_bwd.restype = C.c_int
-        L.invr_expand_row_grad.argtypes = [C.POINTER(InvrGrid), vp, vp, vp, vp]
-        L.invr_expand_row_grad.restype = C.c_int
-        L.invr_part_encode_bwd_lists.argtypes = [C.POINTER(InvrGrid), vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
-        L.invr_part_encode_bwd_lists.restype = C.c_int
-        L.invr_train_loss_fwd.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp, vp]
-        L.invr_train_loss_bwd.argtypes = [vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, vp, vp, vp, vp, vp]
-        L.invr_train_loss_fwd.restype = L.invr_train_loss_bwd.restype = C.c_int
-        L.invr_knn_neighbors.argtypes = [C.POINTER(InvrScene), vp, C.c_int64, vp, vp, vp, vp, vp]
-        L.invr_knn_neighbors.restype = C.c_int
-        L.invr_pose_points.argtypes = [C.POINTER(InvrScene), vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, C.c_int64, vp, vp, vp]
-        L.invr_pose_points.restype = C.c_int
-        L.invr_warp_deform.argtypes = [C.POINTER(InvrScene), C.POINTER(InvrModel), vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp]
-        L.invr_part_field_fwd.argtypes = [C.POINTER(InvrModel), C.c_int32, vp, vp, vp, C.c_int64, vp, vp, C.c_size_t, vp]
-        L.invr_part_encode_workspace.restype = C.c_size_t
-        L.invr_part_encode_workspace.argtypes = [C.c_int64]
-        L.invr_part_encode_fwd.argtypes = [C.POINTER(InvrGrid), vp, C.c_int64, C.c_int32, vp, vp, C.c_size_t, vp]
-        L.invr_composite_fwd.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp, vp]
-        L.invr_workspace_layout.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.POINTER(InvrWsLayout)]
-        L.invr_deform_fwd.argtypes = [C.POINTER(InvrScene), C.POINTER(InvrModel), vp, C.c_int64, vp, vp]
-        L.invr_distortion_fwd.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, vp]
-        L.invr_grid_encode_bwd.argtypes = [C.POINTER(InvrGrid), vp, vp, C.c_int64, vp, vp, vp, vp]
-        L.invr_composite_bwd.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp]
-        for n in ('invr_workspace_layout', 'invr_deform_fwd', 'invr_distortion_fwd', 'invr_grid_encode_bwd', 'invr_composite_bwd'):
-            getattr(L, n).restype = C.c_int
-        L.invr_geometry_fwd.argtypes = [C.POINTER(InvrScene), C.POINTER(InvrModel), vp, vp, vp, vp, vp, C.c_int64, C.c_int32,
-                                        vp, vp, vp, C.c_size_t, C.c_int64, vp]
-        L.invr_geometry_fwd.restype = C.c_int
-        dp = C.POINTER(C.c_double)
-        L.invr_generate_rays.argtypes = [dp, dp, dp, dp, C.POINTER(C.c_float), C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
-        L.invr_generate_rays.restype = C.c_int
-        L.invr_grid_row_sums_len.argtypes = [vp]
-        L.invr_grid_row_sums_len.restype = C.c_int64
-        L.invr_grid_row_sums.argtypes = [vp, vp, vp]
-        L.invr_grid_row_sums.restype = C.c_int
-        L.invr_part_mlp_fwd.argtypes = [C.POINTER(InvrModel), C.c_int32, vp, vp, vp, C.c_int64, vp, vp, vp]
-        L.invr_part_mlp_fwd.restype = C.c_int
-        L.invr_part_mlp_bwd.argtypes = [C.POINTER(InvrModel), C.c_int32, vp, vp, vp, C.c_int64, vp, C.POINTER(InvrMlpBwdOut), vp]
-        L.invr_part_mlp_bwd.restype = C.c_int
-        L.invr_part_mlp_bwd_lists.argtypes = [C.POINTER(InvrModel), C.c_int32, vp, vp, vp, C.c_int64, C.c_int64, vp, vp, vp,
-                                              C.POINTER(InvrMlpBwdOut), C.c_int32, vp]
-        L.invr_part_mlp_bwd_lists.restype = C.c_int
-        L.invr_part_wgrad.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(vp), C.POINTER(vp), vp, vp]
-        L.invr_part_wgrad.restype = C.c_int
-        L.invr_adam_chunk_elems.restype = C.c_int32
-        L.invr_adam_step.argtypes = [vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_float, vp]
-        L.invr_adam_step.restype = C.c_int
-        L.invr_rigid_transformation.argtypes = [vp, vp, vp, vp, vp]
-        L.invr_rigid_transformation.restype = C.c_int
-        L.invr_pack_parts.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, vp, vp, vp, vp, vp]
-        L.invr_pack_parts.restype = C.c_int
-        L.invr_field_workspace_bytes.restype = C.c_size_t
-        L.invr_field_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-        L.invr_field_fwd.argtypes = [C.POINTER(InvrScene), C.POINTER(InvrModel), vp, vp, C.c_int64, vp, vp, vp, vp, C.c_size_t, C.c_int64, vp]
-        L.invr_field_fwd.restype = C.c_int
-        L.invr_eval_workspace_bytes.restype = C.c_size_t
-        L.invr_eval_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
-        L.invr_image_assemble.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-        L.invr_image_metrics.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_size_t, vp]
-        L.invr_image_assemble.restype = L.invr_image_metrics.restype = C.c_int
-        L.invr_profile_enable.argtypes = [C.c_int32]
-        L.invr_profile_read.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-        for n in ('invr_render_fwd', 'invr_grid_encode_fwd', 'invr_sample_volume', 'invr_knn_blend',
-                  'invr_warp_deform', 'invr_part_field_fwd', 'invr_composite_fwd'):
-            getattr(L, n).restype = C.c_int
         _lib = L
     return _lib
 

@@ -1,8 +1,8 @@
-// Device bodies shared by the stand-alone kernels (k_cull.hip, k_warp.hip) and by the two fused front-of-frame launches of
-// k_knn.hip (k_front_scene: KNN index build + cull cell mask + per-vertex matrices + deformer t-slices as workgroup ranges of ONE
-// launch; k_front_cull: lattice-cell classification + cull flags as workgroup ranges of one launch).  A fork / join through a side
-// stream costs 10-17 us per edge under hipGraph replay on this runtime (gpurun_out/r4c: 74 us of a 0.56 ms ray shard), launches
-// that follow each other on one stream start back to back — so independent small kernels share a launch instead of a stream.
+// Device bodies of the two fused front-of-frame launches of k_knn.hip — k_front_scene: KNN index build + cull cell mask + per-vertex
+// matrices + deformer t-slices as workgroup ranges of ONE launch; k_front_cull: lattice-cell classification + cull flags as workgroup
+// ranges of one launch — and of the two stand-alone kernels that frames without the masked cull still run (k_cull_flag,
+// k_knn_voxel_class).  A fork / join through a second stream cost 10-17 us per edge under hipGraph replay on this runtime (74 us of a
+// 0.56 ms ray shard), launches that follow each other on one stream start back to back — so independent small kernels share a launch.
 #pragma once
 #include "pipeline.h"
 
@@ -15,8 +15,8 @@
 // cannot hold a survivor — 93 % of the samples of the bench frame then skip the 8 taps.  Cell (x0,y0,z0) pairs
 // with corner x1 = min(x0+1, dx-1) exactly as the border-clamped sampler does, so there are dx*dy*dz cells.
 // The live cells are also appended to a list (wave-aggregated: one atomic per wave), which the KNN's per-cell classification
-// (k_knn_voxel_class, side stream) walks instead of the whole lattice.
-// (body: `i` = the thread's cell; called with whole waves by k_cull_cells and by the scene-setup launch k_front_scene, k_knn.hip)
+// (voxel_class_body, k_knn.hip) walks instead of the whole lattice.
+// (body: `i` = the thread's cell; called with whole waves by the scene-setup launch k_front_scene, k_knn.hip)
 __device__ __forceinline__ void cull_cells_body(const VolDev& v, float thresh_hi, uint8_t* __restrict__ mask, int32_t* __restrict__ live,
                                                 int32_t* __restrict__ n_live, uint8_t* __restrict__ voxcls, const int i) {
     const bool in = i < v.dx * v.dy * v.dz;

@@ -145,8 +145,26 @@ static int check_mlp_deform(const InvrMlp* m) {
     return 0;
 }
 
+static int check_deformer(const InvrModel* m) { return check_grid(&m->deform_grid, "deformer grid") || check_mlp_deform(&m->deform_mlp); }
+
+// the deformer of the kernels that hold the grid's per-frame t-slices (k_warp.hip)
+static int check_deformer_slices(const InvrModel* m) {
+    if (check_deformer(m)) return 1;
+    INVR_CHECK(m->deform_grid.n_levels == 8 && m->deform_grid.n_features == 2 && !m->deform_grid.sum && m->deform_grid.include_input,
+               "deformer grid must be 8 levels x 2 features, sum=False, include_input");
+    return 0;
+}
+
+// kernel arguments of a call without ray geometry: the scene and the sizes, every pointer null
+static RenderArgs scene_args(const InvrScene* scene, int64_t n_rays, int32_t n_samples) {
+    RenderArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scene = make_scene_dev(scene);
+    a.R = n_rays; a.S = n_samples; a.N = n_rays * (int64_t)n_samples;
+    return a;
+}
+
 // ---- per-stage HIP-event profiling -----------------------------------------------------------------
-#include <vector>
 struct ProfInterval { int stage; hipEvent_t t0, t1; };
 static bool g_prof_on = false;
 static int g_prof_renders = 0;
@@ -204,6 +222,12 @@ struct Carver {
 
 // counters + per-group pair counts, cleared by one memset per frame: a multiple of 256 bytes (an odd size splits the fill in two launches)
 static size_t counters_ints(int64_t n_groups) { return align_up((size_t)CNT_ALLOC + (size_t)n_groups * INVR_NUM_PARTS, 64); }
+
+// survivor capacity of a call: max_active <= 0 or beyond N means "every ray-sample"
+static int64_t clamp_active(int64_t N, int64_t max_active) {
+    if (max_active <= 0 || max_active > N) max_active = N;
+    return max_active < 1 ? 1 : max_active;
+}
 
 #define KNN_MAX_PART 8192
 static size_t carve(Workspace& w, void* base, int64_t N, int64_t cap) {
@@ -266,11 +290,9 @@ static size_t carve(Workspace& w, void* base, int64_t N, int64_t cap) {
 extern "C" int invr_workspace_layout(int64_t n_rays, int32_t n_samples, int64_t max_active, InvrWsLayout* o) {
     INVR_CHECK(o != nullptr, "invr_workspace_layout: null output");
     Workspace w;
-    int64_t N = n_rays * (int64_t)n_samples;
-    if (max_active <= 0 || max_active > N) max_active = N;
-    if (max_active < 1) max_active = 1;
+    const int64_t N = n_rays * (int64_t)n_samples > 0 ? n_rays * (int64_t)n_samples : 1;
     char* base = reinterpret_cast<char*>(uintptr_t(1) << 40);        // dummy non-null base: only offsets are used
-    carve(w, base, N > 0 ? N : 1, max_active);
+    carve(w, base, N, clamp_active(N, max_active));
     auto off = [&](const void* p) { return (int64_t)(reinterpret_cast<const char*>(p) - base); };
     o->cap = w.cap; o->lcap = w.lcap;
     o->counters = off(w.counters); o->active_idx = off(w.active_idx); o->word_off = off(w.word_off); o->mask = off(w.mask);
@@ -287,10 +309,8 @@ extern "C" int invr_workspace_layout(int64_t n_rays, int32_t n_samples, int64_t 
 
 extern "C" size_t invr_workspace_bytes(int64_t n_rays, int32_t n_samples, int64_t max_active) {
     Workspace w;
-    int64_t N = n_rays * (int64_t)n_samples;
-    if (max_active <= 0 || max_active > N) max_active = N;
-    if (max_active < 1) max_active = 1;
-    return carve(w, nullptr, N > 0 ? N : 1, max_active);
+    const int64_t N = n_rays * (int64_t)n_samples > 0 ? n_rays * (int64_t)n_samples : 1;
+    return carve(w, nullptr, N, clamp_active(N, max_active));
 }
 
 __global__ void k_export_stats(const int32_t* counters, int32_t* stats) {
@@ -329,28 +349,45 @@ static PartStreams* part_streams() {
     return &ps;
 }
 
-static int render_impl(const InvrScene* scene, const InvrModel* model,
-                       const float* ray_o, const float* ray_d, const float* near, const float* far,
-                       const float* jitter, const float* wpts, const float* wdirs, int64_t n_rays, int32_t n_samples,
-                       float* rgb_map, float* acc_map, float* raw, float* occ, float* weights,
-                       float* z_vals, int32_t* stats,
-                       void* workspace, size_t workspace_bytes, int64_t max_active, void* stream,
-                       bool geometry_only = false, bool may_reorder = false, uint64_t* raw_dirty = nullptr) {
-    hipStream_t st = (hipStream_t)stream;
+// One frame through the pipeline, as its five entry points describe it: a zero-initialised aggregate, every caller fills what it has.
+struct FrameCall {
+    const InvrScene* scene;
+    const InvrModel* model;
+    const float *ray_o, *ray_d, *near, *far, *jitter;      // ray inputs (n_rays rays of n_samples samples) ...
+    const float *wpts, *wdirs;                              // ... or point inputs (n_rays points, n_samples == 1)
+    int64_t n_rays;
+    int32_t n_samples;
+    float *rgb_map, *acc_map, *raw, *occ, *weights, *z_vals;      // outputs (NULL to skip; rgb_map / acc_map required unless geometry_only)
+    int32_t* stats;
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t max_active;
+    void* stream;
+    bool geometry_only;      // stop behind the warp: pair lists, flags, counters and z_vals only
+    bool may_reorder;        // an eval call: the depth-windowed survivor order is allowed (the training calls keep ray-major)
+    uint64_t* raw_dirty;     // invr_render_fwd_tracked: raw's zero rows are tracked, not rewritten
+};
+
+static int render_impl(const FrameCall& c) {
+    const InvrScene* scene = c.scene;
+    const InvrModel* model = c.model;
+    const float* wpts = c.wpts;
+    const int64_t n_rays = c.n_rays;
+    const int32_t n_samples = c.n_samples;
+    void* workspace = c.workspace;
+    hipStream_t st = (hipStream_t)c.stream;
     INVR_CHECK(scene && model, "invr_render_fwd: null scene/model");
     INVR_CHECK(n_rays >= 0 && (n_samples >= 2 || (wpts && n_samples == 1)), "invr_render_fwd: need n_rays >= 0 and n_samples >= 2");
     if (n_rays == 0) return 0;
-    INVR_CHECK(((ray_o && ray_d && near && far) || (wpts && wdirs)) && (geometry_only || (rgb_map && acc_map)), "invr_render_fwd: null ray/output pointer");
+    INVR_CHECK(((c.ray_o && c.ray_d && c.near && c.far) || (wpts && c.wdirs)) && (c.geometry_only || (c.rgb_map && c.acc_map)), "invr_render_fwd: null ray/output pointer");
     const int64_t N = n_rays * (int64_t)n_samples;
     INVR_CHECK(N < (1ll << 31), "invr_render_fwd: n_rays*n_samples must be < 2^31 (got %lld); split the ray list", (long long)N);
-    if (max_active <= 0 || max_active > N) max_active = N;
+    const int64_t max_active = clamp_active(N, c.max_active);
     Workspace w;
     size_t need = carve(w, workspace, N, max_active);
-    INVR_CHECK(workspace != nullptr && workspace_bytes >= need, "invr_render_fwd: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    INVR_CHECK(workspace != nullptr && c.workspace_bytes >= need, "invr_render_fwd: workspace too small (%zu < %zu bytes)", c.workspace_bytes, need);
     INVR_CHECK(((uintptr_t)workspace & 255) == 0, "invr_render_fwd: workspace must be 256-byte aligned");
-    if (check_grid(&model->deform_grid, "deformer grid") || check_mlp_deform(&model->deform_mlp)) return 1;
-    INVR_CHECK(model->deform_grid.n_levels == 8 && model->deform_grid.n_features == 2 && !model->deform_grid.sum &&
-               model->deform_grid.include_input, "deformer grid must be 8 levels x 2 features, sum=False, include_input");
+    if (check_deformer_slices(model)) return 1;
     for (int p = 0; p < INVR_NUM_PARTS; ++p) if (check_grid(&model->part[p].grid, "part grid")) return 1;
     INVR_CHECK(scene->pbw_channels >= 1 && scene->part_stride >= 1, "invr_render_fwd: bad scene dims");
     INVR_CHECK(scene->tpose_viewdir, "invr_render_fwd: tpose_viewdir=False is not supported (the reference cannot run it either: "
@@ -364,15 +401,13 @@ static int render_impl(const InvrScene* scene, const InvrModel* model,
     // noise and its (Na*P, .) outputs are defined on it).
     // INVR_ORDER is the library's only runtime switch (0 = ray-major everywhere: tools/ab_order.sh, tests/test_gpu_fullsize.py)
     static const int order_env = getenv("INVR_ORDER") ? atoi(getenv("INVR_ORDER")) : 1;
-    if (order_env && may_reorder && !wpts && !jitter && !weights && n_samples >= 8 && n_samples <= 1024 && (n_samples & (n_samples - 1)) == 0) {
+    if (order_env && c.may_reorder && !wpts && !c.jitter && !c.weights && n_samples >= 8 && n_samples <= 1024 && (n_samples & (n_samples - 1)) == 0) {
         w.ord_cols = n_samples / 8;
         w.ord_rows = 1024 / w.ord_cols;
     }
-    RenderArgs a;
-    a.scene = make_scene_dev(scene);
-    a.ray_o = ray_o; a.ray_d = ray_d; a.near = near; a.far = far; a.jitter = jitter; a.z_vals = z_vals;
-    a.wpts = wpts; a.wdirs = wdirs;
-    a.R = n_rays; a.S = n_samples; a.N = N;
+    RenderArgs a = scene_args(scene, n_rays, n_samples);
+    a.ray_o = c.ray_o; a.ray_d = c.ray_d; a.near = c.near; a.far = c.far; a.jitter = c.jitter; a.z_vals = c.z_vals;
+    a.wpts = wpts; a.wdirs = c.wdirs;
 
     // The front of the frame on the caller's stream (k_knn.hip "the front of a frame as two launches"): one memset, one launch for
     // everything that depends on the scene alone (KNN index, cull cell mask + live-cell list, per-vertex matrices, deformer slices),
@@ -382,16 +417,15 @@ static int render_impl(const InvrScene* scene, const InvrModel* model,
     GridDev dgrid = make_grid_dev(&model->deform_grid);
     {
         ProfStage ps(INVR_STAGE_CULL, st);
-        int have_cells = 0, flags_done = 0;
-        if (launch_front_scene(a, w, dgrid, &have_cells, st)) return 1;
-        if (!have_cells) { w.knn.voxcls = nullptr; w.knn.voxmask = nullptr; }
-        else if (launch_front_cull(a, w, &flags_done, st)) return 1;
-        if (w.knn.voxcls && !flags_done && launch_knn_voxel_class(a, w, st)) return 1;      // (small calls: the cull runs unmasked)
-        if (launch_cull(a, w, max_active, have_cells != 0, flags_done != 0, st)) return 1;
+        const FrontPlan fp = plan_front(a);
+        if (launch_front_scene(a, w, dgrid, fp, st)) return 1;
+        if (!fp.have_cells) { w.knn.voxcls = nullptr; w.knn.voxmask = nullptr; }      // (the KNN runs without lattice-cell classes)
+        else if (fp.masked ? launch_front_cull(a, w, fp, st) : launch_knn_voxel_class(a, w, st)) return 1;      // (small calls: the cull runs unmasked)
+        if (launch_cull(a, w, max_active, fp, st)) return 1;
     }
     {
         ProfStage ps(INVR_STAGE_KNN, st);
-        if (launch_knn_pairs(a, w, stats, st)) return 1;
+        if (launch_knn_pairs(a, w, c.stats, st)) return 1;
         if (scene->aggr >= INVR_AGGR_DIST && launch_knn_pdist(a, w, st)) return 1;
     }
     {
@@ -399,7 +433,7 @@ static int render_impl(const InvrScene* scene, const InvrModel* model,
         MlpDev dm = make_mlp_dev(&model->deform_mlp);
         if (launch_warp_pairs(a, w, dgrid, dm, st)) return 1;
     }
-    if (!geometry_only) {
+    if (!c.geometry_only) {
         // The five parts in one encoder launch and one launch per MLP phase (stage times are booked on part 0).  Eval reads the
         // row-sum tables; the training forward / eval without row sums read the trainable 64-byte rows — a part's 1e4-5e4 pairs
         // make short, latency-bound launches, so the parts also run side by side there (the profiler keeps per-part
@@ -429,9 +463,9 @@ static int render_impl(const InvrScene* scene, const InvrModel* model,
         }
         { ProfStage ps(INVR_STAGE_MLP, st); if (launch_part_mlp_all(ma, w, st)) return 1; }
     }
-    if (!geometry_only) {
+    if (!c.geometry_only) {
         ProfStage ps(INVR_STAGE_COMPOSITE, st);
-        if (launch_merge_composite(a, w, rgb_map, acc_map, raw, occ, weights, st, reinterpret_cast<unsigned long long*>(raw_dirty))) return 1;
+        if (launch_merge_composite(a, w, c.rgb_map, c.acc_map, c.raw, c.occ, c.weights, st, reinterpret_cast<unsigned long long*>(c.raw_dirty))) return 1;
     }
     if (g_prof_on) ++g_prof_renders;
     return 0;                   // (stats were exported by the KNN stage: the counters are final once the pair lists are)
@@ -443,8 +477,14 @@ extern "C" int invr_render_fwd(const InvrScene* scene, const InvrModel* model,
                                float* rgb_map, float* acc_map, float* raw, float* occ, float* weights,
                                float* z_vals, int32_t* stats,
                                void* workspace, size_t workspace_bytes, int64_t max_active, void* stream) {
-    return render_impl(scene, model, ray_o, ray_d, near, far, jitter, nullptr, nullptr, n_rays, n_samples, rgb_map, acc_map,
-                       raw, occ, weights, z_vals, stats, workspace, workspace_bytes, max_active, stream, false, true);
+    FrameCall c = {};
+    c.scene = scene; c.model = model;
+    c.ray_o = ray_o; c.ray_d = ray_d; c.near = near; c.far = far; c.jitter = jitter;
+    c.n_rays = n_rays; c.n_samples = n_samples;
+    c.rgb_map = rgb_map; c.acc_map = acc_map; c.raw = raw; c.occ = occ; c.weights = weights; c.z_vals = z_vals; c.stats = stats;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.max_active = max_active; c.stream = stream;
+    c.may_reorder = true;
+    return render_impl(c);
 }
 
 extern "C" size_t invr_raw_dirty_bytes(int64_t rows) { return rows > 0 ? (size_t)cdiv(rows, 64) * sizeof(uint64_t) : 0; }
@@ -461,16 +501,29 @@ extern "C" int invr_render_fwd_tracked(const InvrScene* scene, const InvrModel* 
     INVR_CHECK(n_rays >= 0 && n_samples >= 1 && raw_rows >= n_rays * (int64_t)n_samples, "invr_render_fwd_tracked: raw_rows %lld < n_rays * n_samples",
                (long long)raw_rows);
     INVR_CHECK(((uintptr_t)raw & 15) == 0 && ((uintptr_t)raw_dirty & 7) == 0, "invr_render_fwd_tracked: raw must be 16-byte, raw_dirty 8-byte aligned");
-    return render_impl(scene, model, ray_o, ray_d, near, far, jitter, nullptr, nullptr, n_rays, n_samples, rgb_map, acc_map,
-                       raw, nullptr, nullptr, z_vals, stats, workspace, workspace_bytes, max_active, stream, false, true, raw_dirty);
+    FrameCall c = {};
+    c.scene = scene; c.model = model;
+    c.ray_o = ray_o; c.ray_d = ray_d; c.near = near; c.far = far; c.jitter = jitter;
+    c.n_rays = n_rays; c.n_samples = n_samples;
+    c.rgb_map = rgb_map; c.acc_map = acc_map; c.raw = raw; c.z_vals = z_vals; c.stats = stats;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.max_active = max_active; c.stream = stream;
+    c.may_reorder = true;
+    c.raw_dirty = raw_dirty;
+    return render_impl(c);
 }
 
 extern "C" int invr_geometry_fwd(const InvrScene* scene, const InvrModel* model,
                                  const float* ray_o, const float* ray_d, const float* near, const float* far,
                                  const float* jitter, int64_t n_rays, int32_t n_samples, float* z_vals, int32_t* stats,
                                  void* workspace, size_t workspace_bytes, int64_t max_active, void* stream) {
-    return render_impl(scene, model, ray_o, ray_d, near, far, jitter, nullptr, nullptr, n_rays, n_samples, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, z_vals, stats, workspace, workspace_bytes, max_active, stream, true);
+    FrameCall c = {};
+    c.scene = scene; c.model = model;
+    c.ray_o = ray_o; c.ray_d = ray_d; c.near = near; c.far = far; c.jitter = jitter;
+    c.n_rays = n_rays; c.n_samples = n_samples;
+    c.z_vals = z_vals; c.stats = stats;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.max_active = max_active; c.stream = stream;
+    c.geometry_only = true;
+    return render_impl(c);
 }
 
 extern "C" size_t invr_field_workspace_bytes(int64_t n_points, int64_t max_active) {
@@ -485,8 +538,13 @@ extern "C" int invr_field_fwd(const InvrScene* scene, const InvrModel* model, co
     const size_t inner = invr_workspace_bytes(n_points, 1, max_active);
     INVR_CHECK(workspace && workspace_bytes >= invr_field_workspace_bytes(n_points, max_active), "invr_field_fwd: workspace too small");
     float* scratch = reinterpret_cast<float*>(static_cast<char*>(workspace) + inner);     // rgb_map (n,3) + acc_map (n)
-    return render_impl(scene, model, nullptr, nullptr, nullptr, nullptr, nullptr, wpts, viewdir, n_points, 1,
-                       scratch, scratch + 3 * n_points, raw, occ, nullptr, nullptr, stats, workspace, inner, max_active, stream);
+    FrameCall c = {};
+    c.scene = scene; c.model = model;
+    c.wpts = wpts; c.wdirs = viewdir;
+    c.n_rays = n_points; c.n_samples = 1;
+    c.rgb_map = scratch; c.acc_map = scratch + 3 * n_points; c.raw = raw; c.occ = occ; c.stats = stats;
+    c.workspace = workspace; c.workspace_bytes = inner; c.max_active = max_active; c.stream = stream;
+    return render_impl(c);
 }
 
 // ---- stage-level entry points -------------------------------------------------------------------
@@ -529,11 +587,8 @@ extern "C" int invr_pose_points(const InvrScene* scene, const float* ray_o, cons
     INVR_CHECK(scene && (n == 0 || (ray_o && ray_d && near && far && pose_pts)), "invr_pose_points: null pointer");
     INVR_CHECK(n_rays >= 0 && n_samples >= 2 && n_rays * (int64_t)n_samples < (1ll << 31), "invr_pose_points: bad n_rays / n_samples");
     INVR_CHECK(sample_idx || n == n_rays * (int64_t)n_samples, "invr_pose_points: without sample_idx n must be n_rays*n_samples");
-    RenderArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene = make_scene_dev(scene);
+    RenderArgs a = scene_args(scene, n_rays, n_samples);
     a.ray_o = ray_o; a.ray_d = ray_d; a.near = near; a.far = far; a.jitter = jitter;
-    a.R = n_rays; a.S = n_samples; a.N = n_rays * (int64_t)n_samples;
     return launch_pose_points(a, sample_idx, n, pose_pts, pose_dirs, (hipStream_t)stream);
 }
 
@@ -541,7 +596,7 @@ extern "C" int invr_warp_deform(const InvrScene* scene, const InvrModel* model, 
                                 const float* pose_dirs, const float* bw, const uint8_t* flag, int64_t n,
                                 float* tpose, float* tdirs, float* resd, void* stream) {
     INVR_CHECK(scene && model && (n == 0 || (pose_pts && pose_dirs && bw && flag && tpose && tdirs && resd)), "invr_warp_deform: null pointer");
-    if (check_grid(&model->deform_grid, "deformer grid") || check_mlp_deform(&model->deform_mlp)) return 1;
+    if (check_deformer(model)) return 1;
     return launch_warp_deform_dense(make_scene_dev(scene), make_grid_dev(&model->deform_grid), make_mlp_dev(&model->deform_mlp),
                                     pose_pts, pose_dirs, bw, flag, n, tpose, tdirs, resd, (hipStream_t)stream);
 }
@@ -637,9 +692,7 @@ extern "C" int invr_part_encode_fwd(const InvrGrid* grid, const float* xyz, int6
 extern "C" int invr_deform_fwd(const InvrScene* scene, const InvrModel* model, const float* pts, int64_t n, float* resd,
                                void* stream) {
     INVR_CHECK(scene && model && (n == 0 || (pts && resd)), "invr_deform_fwd: null pointer");
-    if (check_grid(&model->deform_grid, "deformer grid") || check_mlp_deform(&model->deform_mlp)) return 1;
-    INVR_CHECK(model->deform_grid.n_levels == 8 && model->deform_grid.n_features == 2 && !model->deform_grid.sum &&
-               model->deform_grid.include_input, "deformer grid must be 8 levels x 2 features, sum=False, include_input");
+    if (check_deformer_slices(model)) return 1;
     return launch_deform_points(make_scene_dev(scene), make_grid_dev(&model->deform_grid), make_mlp_dev(&model->deform_mlp),
                                 pts, n, resd, (hipStream_t)stream);
 }
@@ -764,12 +817,8 @@ extern "C" int invr_part_mlp_bwd(const InvrModel* model, int32_t pid, const int6
     INVR_CHECK(model && latent_index && pid >= 0 && pid < INVR_NUM_PARTS && out, "invr_part_mlp_bwd: bad model/pid/out");
     if (n == 0) return 0;
     PartMlpDev pm = make_part_mlp(model, pid, latent_index);
+    if (!part_mlp_supported(pm)) return 1;
     INVR_CHECK(emb_soa && dirs_soa && g_raw && out->g_emb && out->gz && out->a && out->g_latent && out->n_pad >= n, "invr_part_mlp_bwd: null pointer / n_pad < n");
-    const MlpDev& oc = pm.occ;
-    const MlpDev& r = pm.rgb;
-    INVR_CHECK(oc.n_linear == 2 && oc.dims[0] == 19 && oc.dims[1] == 64 && oc.dims[2] == 17 && (r.n_linear == 2 || r.n_linear == 3) &&
-               r.dims[0] == 70 && r.dims[1] == 64 && r.dims[r.n_linear] == 3 && pm.n_freq == 4 && pm.latent_dim == 8 && pm.geo_dim == 16,
-               "invr_part_mlp_bwd: supports occ 19-64-17 and rgb 70-64(-64)-3");
     MlpBwdOut o{out->g_emb, out->gz, out->a, out->n_pad, out->g_latent, 0};
     return launch_part_mlp_bwd(pm, emb_soa, dirs_soa, n, n, nullptr, g_raw, nullptr, pid, o, (hipStream_t)stream);
 }
@@ -783,13 +832,9 @@ extern "C" int invr_part_mlp_bwd_lists(const InvrModel* model, int32_t pid, cons
     INVR_CHECK(n_max >= 0 && n_max <= stride && n_max < (1ll << 31), "invr_part_mlp_bwd_lists: 0 <= n_max <= stride required");
     if (n_max == 0) return 0;
     PartMlpDev pm = make_part_mlp(model, pid, latent_index);
+    if (!part_mlp_supported(pm)) return 1;
     INVR_CHECK(emb_soa && dirs_soa && g_raws && out->g_emb && out->gz && out->a && out->g_latent && out->n_pad >= n_max,
                "invr_part_mlp_bwd_lists: null pointer / n_pad < n_max");
-    const MlpDev& oc = pm.occ;
-    const MlpDev& r = pm.rgb;
-    INVR_CHECK(oc.n_linear == 2 && oc.dims[0] == 19 && oc.dims[1] == 64 && oc.dims[2] == 17 && (r.n_linear == 2 || r.n_linear == 3) &&
-               r.dims[0] == 70 && r.dims[1] == 64 && r.dims[r.n_linear] == 3 && pm.n_freq == 4 && pm.latent_dim == 8 && pm.geo_dim == 16,
-               "invr_part_mlp_bwd_lists: supports occ 19-64-17 and rgb 70-64(-64)-3");
     MlpBwdOut o{out->g_emb, out->gz, out->a, out->n_pad, out->g_latent, latent_full ? 1 : 0};
     return launch_part_mlp_bwd(pm, emb_soa, dirs_soa, n_max, stride, count, g_raws, l_slot, pid, o, (hipStream_t)stream);
 }
@@ -833,18 +878,18 @@ static size_t carve_train(TrainWs& t, void* base, size_t off0, int64_t N, int64_
     return align_up(c.off, 256);
 }
 
-static int64_t clamp_active(int64_t N, int64_t max_active) {
-    if (max_active <= 0 || max_active > N) max_active = N;
-    return max_active < 1 ? 1 : max_active;
+// the render workspace followed by the training workspace of one iteration -> total bytes (base NULL: sizes only)
+static size_t carve_iteration(Workspace& w, TrainWs& t, void* base, int64_t n_rays, int32_t n_samples, int64_t max_active) {
+    const int64_t N = n_rays * (int64_t)n_samples > 0 ? n_rays * (int64_t)n_samples : 1;
+    const int64_t cap = clamp_active(N, max_active);
+    const size_t inner = carve(w, base, N, cap);
+    return carve_train(t, base, inner, N, cap + 1);
 }
 
 extern "C" size_t invr_train_workspace_bytes(int64_t n_rays, int32_t n_samples, int64_t max_active) {
-    const int64_t N = n_rays * (int64_t)n_samples > 0 ? n_rays * (int64_t)n_samples : 1;
-    const int64_t cap = clamp_active(N, max_active);
     Workspace w;
     TrainWs t;
-    const size_t inner = carve(w, nullptr, N, cap);
-    return carve_train(t, nullptr, inner, N, cap + 1);
+    return carve_iteration(w, t, nullptr, n_rays, n_samples, max_active);
 }
 
 extern "C" int invr_train_fwd(const InvrScene* scene, const InvrModel* model,
@@ -858,26 +903,22 @@ extern "C" int invr_train_fwd(const InvrScene* scene, const InvrModel* model,
     INVR_HIP(hipMemsetAsync(terms, 0, TERM_LEN * sizeof(float), st));
     if (n_rays == 0) return 0;
     INVR_CHECK(raw && weights && z_vals, "invr_train_fwd: raw, weights and z_vals are required (the backward reads them)");
-    const int64_t N = n_rays * (int64_t)n_samples;
-    const int64_t cap = clamp_active(N, max_active);
-    INVR_CHECK(workspace && workspace_bytes >= invr_train_workspace_bytes(n_rays, n_samples, max_active), "invr_train_fwd: workspace too small");
-    INVR_CHECK(!pair_noise || pair_noise_rows >= cap * INVR_NUM_PARTS, "invr_train_fwd: pair_noise needs >= %lld rows", (long long)(cap * INVR_NUM_PARTS));
-    for (int p = 0; p < INVR_NUM_PARTS; ++p)
-        INVR_CHECK(model->part[p].grid.row_sums == nullptr, "invr_train_fwd: training reads the trainable 64-byte rows (row_sums must be NULL)");
-    const size_t inner = invr_workspace_bytes(n_rays, n_samples, max_active);
-    if (render_impl(scene, model, ray_o, ray_d, near, far, jitter, nullptr, nullptr, n_rays, n_samples, rgb_map, acc_map, raw, occ, weights,
-                    z_vals, nullptr, workspace, inner, max_active, stream))
-        return 1;
     Workspace w;
     TrainWs t;
-    carve(w, workspace, N, cap);
-    carve_train(t, workspace, inner, N, cap + 1);
+    INVR_CHECK(workspace && workspace_bytes >= carve_iteration(w, t, workspace, n_rays, n_samples, max_active), "invr_train_fwd: workspace too small");
     t.terms = terms;
+    INVR_CHECK(!pair_noise || pair_noise_rows >= w.cap * INVR_NUM_PARTS, "invr_train_fwd: pair_noise needs >= %lld rows", (long long)(w.cap * INVR_NUM_PARTS));
+    for (int p = 0; p < INVR_NUM_PARTS; ++p)
+        INVR_CHECK(model->part[p].grid.row_sums == nullptr, "invr_train_fwd: training reads the trainable 64-byte rows (row_sums must be NULL)");
+    FrameCall c = {};          // (stats are exported below, behind the terms; ray-major order: may_reorder stays false)
+    c.scene = scene; c.model = model;
+    c.ray_o = ray_o; c.ray_d = ray_d; c.near = near; c.far = far; c.jitter = jitter;
+    c.n_rays = n_rays; c.n_samples = n_samples;
+    c.rgb_map = rgb_map; c.acc_map = acc_map; c.raw = raw; c.occ = occ; c.weights = weights; c.z_vals = z_vals;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.max_active = max_active; c.stream = stream;
+    if (render_impl(c)) return 1;
     if (dist_loss && launch_distortion(weights, z_vals, n_rays, n_samples, dist_loss, st)) return 1;
-    RenderArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene = make_scene_dev(scene);
-    a.R = n_rays; a.S = n_samples; a.N = N;
+    const RenderArgs a = scene_args(scene, n_rays, n_samples);
     if (launch_train_terms(a, w, t, make_grid_dev(&model->deform_grid), make_mlp_dev(&model->deform_mlp), pair_noise, st)) return 1;
     if (stats) {
         hipLaunchKernelGGL(k_export_stats, dim3(1), dim3(64), 0, st, w.counters, stats);
@@ -905,15 +946,13 @@ extern "C" int invr_train_bwd(const InvrScene* scene, const InvrModel* model, in
     INVR_CHECK(scene && model && grads, "invr_train_bwd: null scene / model / grads");
     if (stages == 0) stages = INVR_BWD_ALL;
     if (n_rays == 0) return 0;
+    for (int p = 0; p < INVR_NUM_PARTS; ++p)
+        if ((stages & INVR_BWD_PART(p)) && !part_mlp_supported(make_part_mlp(model, p, scene->latent_index))) return 1;
     INVR_CHECK(raw && weights && z_vals && g_rgb_map, "invr_train_bwd: raw, weights, z_vals and g_rgb_map are required");
     const int64_t N = n_rays * (int64_t)n_samples;
-    const int64_t cap = clamp_active(N, max_active);
-    INVR_CHECK(workspace && workspace_bytes >= invr_train_workspace_bytes(n_rays, n_samples, max_active), "invr_train_bwd: workspace too small");
-    const size_t inner = invr_workspace_bytes(n_rays, n_samples, max_active);
     Workspace w;
     TrainWs t;
-    carve(w, workspace, N, cap);
-    carve_train(t, workspace, inner, N, cap + 1);
+    INVR_CHECK(workspace && workspace_bytes >= carve_iteration(w, t, workspace, n_rays, n_samples, max_active), "invr_train_bwd: workspace too small");
     const int64_t lcap = w.lcap;
     // distortion^T -> compositing^T (-> + direct gradient of raw) -> merge^T
     if (stages & INVR_BWD_HEAD) {
@@ -949,9 +988,6 @@ extern "C" int invr_train_bwd(const InvrScene* scene, const InvrModel* model, in
         const int n_rgb = pm.rgb.n_linear;
         INVR_CHECK(G.row_grad && G.rgb_latent && G.occ_w[0] && G.occ_b[0] && G.occ_w[1] && G.occ_b[1] && G.rgb_w[0] && G.rgb_b[0] &&
                    G.rgb_w[n_rgb - 1] && G.rgb_b[n_rgb - 1], "invr_train_bwd: null gradient pointer (part %d)", p);
-        INVR_CHECK(pm.occ.n_linear == 2 && pm.occ.dims[0] == 19 && pm.occ.dims[1] == 64 && pm.occ.dims[2] == 17 && (n_rgb == 2 || n_rgb == 3) &&
-                   pm.rgb.dims[0] == 70 && pm.rgb.dims[1] == 64 && pm.rgb.dims[n_rgb] == 3 && pm.n_freq == 4 && pm.latent_dim == 8 && pm.geo_dim == 16,
-                   "invr_train_bwd: supports occ 19-64-17 and rgb 70-64(-64)-3");
         const int32_t* count = w.counters + CNT_PAIRS + p;
         MlpBwdOut o{t.g_emb[p], t.gz[p], t.a[p], lcap, G.rgb_latent, 1};
         if (launch_part_mlp_bwd(pm, w.emb[p], w.l_d[p], lcap, lcap, count, reinterpret_cast<const float*>(t.g_raws), w.l_slot[p], p, o, sp)) return 1;
@@ -985,15 +1021,12 @@ extern "C" int invr_train_bwd(const InvrScene* scene, const InvrModel* model, in
     };
     // deformer^T over the listed pairs and the pair-regulariser neighbours (needs the g_x of every part)
     if (!(stages & INVR_BWD_DEFORMER)) return join_wgrads();
-    if (check_grid(&model->deform_grid, "deformer grid") || check_mlp_deform(&model->deform_mlp)) return 1;
+    if (check_deformer(model)) return 1;
     INVR_CHECK(grads->deform_hash && (!model->deform_grid.separate_dense || grads->deform_dense) && grads->deform_w[0] && grads->deform_w[1] &&
                grads->deform_w[2] && grads->deform_b[0] && grads->deform_b[1] && grads->deform_b[2], "invr_train_bwd: null deformer gradient pointer");
     DeformGrads DG{{grads->deform_w[0], grads->deform_w[1], grads->deform_w[2]}, {grads->deform_b[0], grads->deform_b[1], grads->deform_b[2]},
                    grads->deform_dense, grads->deform_hash};
-    RenderArgs a;
-    memset(&a, 0, sizeof(a));
-    a.scene = make_scene_dev(scene);
-    a.R = n_rays; a.S = n_samples; a.N = N;
+    const RenderArgs a = scene_args(scene, n_rays, n_samples);
     // (the deformer's own weight gradients on a library stream beside its grid^T: the stream after the LAST part's, which is free
     // here or busy with the smallest part's weight gradients)
     PartStreams* ds = ps ? ps : part_streams();

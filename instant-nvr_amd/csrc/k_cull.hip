@@ -12,11 +12,6 @@
 
 #include "front_bodies.h"
 
-__global__ void k_cull_cells(VolDev v, float thresh_hi, uint8_t* __restrict__ mask, int32_t* __restrict__ live, int32_t* __restrict__ n_live,
-                             uint8_t* __restrict__ voxcls) {
-    cull_cells_body(v, thresh_hi, mask, live, n_live, voxcls, (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
-
 template <bool MASKED, bool FAST, bool RAY4>
 __global__ __launch_bounds__(CULL_BLOCK) void k_cull_flag(RenderArgs a, Workspace w, double inv_S, float lin_step) {
     cull_flag_body<MASKED, FAST, RAY4>(a, w, inv_S, lin_step, (int64_t)blockIdx.x);
@@ -171,31 +166,13 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_compact_win(RenderArgs a, Worksp
         if (byte0 + j < n_bytes) w.byte_off[byte0 + j] = soff[j];
 }
 
-// cell mask of the cull + list of the live cells (for the KNN's lattice classification); 1 = built
-int launch_cull_cells(const RenderArgs& a, const Workspace& w, hipStream_t st) {
-    const VolDev& v = a.scene.pbw;
-    const int64_t cells = (int64_t)v.dx * v.dy * v.dz;
-    if (cells > CULL_MASK_MAX || cells > VOXMASK_MAX_CELLS) return 0;
-    hipLaunchKernelGGL(k_cull_cells, dim3((unsigned)cdiv(cells, 256)), dim3(256), 0, st, v, a.scene.thresh * (1.0f + 1e-5f), w.cullmask,
-                       w.knn.live_cells, w.counters + CNT_LIVE, w.knn.voxcls);
-    if (hipGetLastError() != hipSuccess) return 0;
-    return 1;
-}
-
-int launch_cull(const RenderArgs& a, const Workspace& w, int64_t max_active, bool have_cells, bool flags_done, hipStream_t st) {
+// Cull flags (unless k_front_cull wrote them: fp.masked), scan, compaction.  Only the UNMASKED flag kernel is launched from here: a
+// frame with a cell mask that pays for itself takes the masked body inside k_front_cull (k_knn.hip), every other frame runs unmasked.
+int launch_cull(const RenderArgs& a, const Workspace& w, int64_t max_active, const FrontPlan& fp, hipStream_t st) {
     int64_t nb = cdiv(a.N, CULL_TILE);
-    const VolDev& v = a.scene.pbw;
-    const int64_t cells = (int64_t)v.dx * v.dy * v.dz;
-    const double inv_S = 1.0 / (double)a.S;
-    const float lin_step = 1.0f / (float)(a.S - 1);                // linspace01's step, the same IEEE division
-    if (flags_done) {
-    } else if (have_cells && a.N >= 4 * cells) {        // the mask pays for itself on full frames only
-        const bool fast = !a.wpts && !a.jitter && a.N < (1ll << 31) && cells * v.c < (1ll << 31) && a.S >= 2 &&
-                      v.dx <= 1024 && v.dy <= 1024 && v.dz <= 1024;      // (front_bodies.h: the pre-test's error bound)
-        if (fast && (a.S & 3) == 0) hipLaunchKernelGGL((k_cull_flag<true, true, true>), dim3((unsigned)nb), dim3(CULL_BLOCK), 0, st, a, w, inv_S, lin_step);
-        else if (fast) hipLaunchKernelGGL((k_cull_flag<true, true, false>), dim3((unsigned)nb), dim3(CULL_BLOCK), 0, st, a, w, inv_S, lin_step);
-        else hipLaunchKernelGGL((k_cull_flag<true, false, false>), dim3((unsigned)nb), dim3(CULL_BLOCK), 0, st, a, w, inv_S, lin_step);
-    } else {
+    if (!fp.masked) {
+        const double inv_S = 1.0 / (double)a.S;
+        const float lin_step = 1.0f / (float)(a.S - 1);                // linspace01's step, the same IEEE division
         hipLaunchKernelGGL((k_cull_flag<false, false, false>), dim3((unsigned)nb), dim3(CULL_BLOCK), 0, st, a, w, inv_S, lin_step);
     }
     INVR_LAUNCH_CHECK();

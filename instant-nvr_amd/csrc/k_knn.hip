@@ -25,10 +25,10 @@
 // pairs.  Exactness: near/band pairs are bit-faithful brute-force results; far pairs differ from
 // the reference by <= 1.1e-9 m in the canonical point (see above).
 //
-// Data layout: a per-frame prepare kernel (k_part_prepare, side stream) Morton-sorts each part's vertices — a counting sort on
+// Data layout: per frame, the first five workgroups of k_front_scene (part_prepare_body) Morton-sort each part's vertices — a counting sort on
 // the 12 leading Morton bits in LDS, every element ranking itself inside its bucket — and writes them pair-interleaved,
 // {x0,x1,y0,y1}{z0,z1,row0,row1} per two vertices, with one {AABB, first vertex} record per 64-vertex cluster and four AABBs of its
-// 16-vertex sub-clusters; k_knn_voxel_class classifies the live lattice cells of the distance volume per part (far / provably
+// 16-vertex sub-clusters; voxel_class_body (a workgroup range of k_front_cull) classifies the live lattice cells of the distance volume per part (far / provably
 // unflagged / undecided + candidate-cluster mask + 4th-nearest bound).  The query kernel (k_knn_pairs) holds the WHOLE index in
 // LDS (persistent 1024-thread workgroups, one per CU); a wave draws tickets of 64 survivors, one thread per point: every vertex /
 // record read is a wave-uniform (broadcast) ds_read_b128, clusters and sub-clusters are pruned per wave with
@@ -44,7 +44,7 @@
 #define KNN_TWO_R2_F 0.01125f
 #define KNN_DFAR2 0.4624f        // (0.68 m)^2, see the header comment: valid while the entries of A / big_A are <= 2 in magnitude
 // The bound above scales with the largest entry M of the frame's A / big_A matrices (|A_bw| <= s M, |x_b| <= s |t_big|): the far
-// distance actually used is derived per frame by k_part_prepare from the matrices themselves — 0.68 m for M <= 2, the distance at
+// distance actually used is derived per frame by part_prepare_body from the matrices themselves — 0.68 m for M <= 2, the distance at
 // which 4 exp(-d^2 / 0.01125) / 1e-8 * M falls to the same 1.1e-9 beyond that, +inf (no folding) for non-finite / absurd
 // matrices — and read by the kernels from ix.dfar2.
 __device__ __forceinline__ float knn_far_dist2(float m_abs) {
@@ -382,11 +382,6 @@ __device__ __forceinline__ void part_prepare_body(const SceneDev& s, const KnnIn
 }
 
 #define PREP_LDS_BYTES ((size_t)(2 * PREP_MAX + 4096) * sizeof(unsigned))
-__global__ __launch_bounds__(PREP_T) void k_part_prepare(SceneDev s, KnnIndex ix) {
-    extern __shared__ unsigned prep_lds[];
-    part_prepare_body(s, ix, (int)blockIdx.x, prep_lds);
-}
-
 // wave-uniform 16-byte LDS read that stays a ds_read_b128 (256 B/clk): when .w is unused the compiler narrows
 // the load to ds_read_b96, which runs at 96 B/clk (MI355X_MICROARCH.md LDS table) — 2x the LDS time
 __device__ __forceinline__ float4 lds_ld4(const float4* p) {
@@ -600,7 +595,7 @@ __global__ __launch_bounds__(KNN_T) void k_knn_pairs(RenderArgs a, Workspace w) 
     __syncthreads();
     KP(6)
     const int na = w.counters[CNT_ACTIVE];
-    const float dfar2 = ix.dfar2[0];                        // far-fold distance^2 of this frame (k_part_prepare)
+    const float dfar2 = ix.dfar2[0];                        // far-fold distance^2 of this frame (part_prepare_body)
     const int lane = threadIdx.x & 63;
     int far_cnt[INVR_NUM_PARTS] = {0, 0, 0, 0, 0};          // far pairs seen by this wave (statistics), flushed once at the end
     // dynamic scheduling, one ticket per wave and 64 survivors: the cost of 64 points varies ~10x with how many clusters they
@@ -909,7 +904,7 @@ __global__ __launch_bounds__(PL_BLOCK) void k_pair_lists(Workspace w, int32_t* _
     if (stats && threadIdx.x < INVR_STATS_LEN) stats[threadIdx.x] = threadIdx.x < CNT_LEN ? w.counters[threadIdx.x] : 0;
 }
 
-// Per-frame classification of the distance-volume lattice cells (side stream, after k_part_prepare): for every cell
+// Per-frame classification of the distance-volume lattice cells (after k_front_scene, which builds the index): for every cell
 // and part, from the box-to-box distance to the cluster AABBs and the cell-centre distance to the cluster
 // representatives, whether EVERY point of the cell is a far pair (lower bound > 0.68 m) or provably unflagged
 // (lower bound >= near_hi and some vertex within band_lo) — the same two tests k_knn_pairs applies per point, so a
@@ -929,7 +924,7 @@ __device__ __forceinline__ void voxel_class_body(const SceneDev& s, const KnnInd
                                                  const int bx, const int n_bx, const int p) {
     const VolDev& v = s.pbw;
     // the live cells — a corner below the cull threshold, 7 % of the lattice on the bench frame; all other cells are never looked
-    // up — were listed by k_cull_cells
+    // up — were listed by cull_cells_body
     const int n_live = n_live_dev[0];
     const float dfar2 = ix.dfar2[0];
     const int per_block = VC_BLOCK / VC_Q;
@@ -1128,18 +1123,6 @@ int launch_knn_voxel_class(const RenderArgs& a, const Workspace& w, hipStream_t 
     return 0;
 }
 
-// The per-frame KNN index only depends on the posed vertices, not on the rays.
-int launch_knn_prepare(const RenderArgs& a, const Workspace& w, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        INVR_HIP(hipFuncSetAttribute((const void*)k_part_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PREP_LDS_BYTES));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(k_part_prepare, dim3(INVR_NUM_PARTS), dim3(PREP_T), PREP_LDS_BYTES, st, a.scene, w.knn);
-    INVR_LAUNCH_CHECK();
-    return 0;
-}
-
 // ---- the front of a frame as two launches on ONE stream ------------------------------------------------------------------------
 // Everything in front of the KNN used to be two chains joined by events: {cell mask -> cull flags -> scan -> compaction} on the
 // caller's stream, {index build -> lattice classes -> vertex matrices -> deformer slices} on a library stream.  Under hipGraph replay
@@ -1173,8 +1156,22 @@ __global__ __launch_bounds__(PREP_T) void k_front_scene(FrontSceneArgs f) {
     deform_slice_body(f.dg, f.si, f.s.frame_dim, f.dslice, b * PREP_T + (int)threadIdx.x);
 }
 
-// -> *have_cells = 1 if the cell mask / live-cell list were built (launch_cull_cells' conditions)
-int launch_front_scene(const RenderArgs& a, const Workspace& w, const GridDev& dg, int* have_cells, hipStream_t st) {
+// The one place that decides how the front of a frame runs (pipeline.h:FrontPlan)
+FrontPlan plan_front(const RenderArgs& a) {
+    const VolDev& v = a.scene.pbw;
+    const int64_t cells = (int64_t)v.dx * v.dy * v.dz;
+    FrontPlan fp;
+    fp.have_cells = !(cells > CULL_MASK_MAX || cells > VOXMASK_MAX_CELLS);
+    fp.masked = fp.have_cells && a.N >= 4 * cells;      // the mask pays for itself on full frames only
+    fp.fast = fp.masked && !a.wpts && !a.jitter && a.N < (1ll << 31) && cells * v.c < (1ll << 31) && a.S >= 2 &&
+              v.dx <= 1024 && v.dy <= 1024 && v.dz <= 1024;      // (front_bodies.h: the pre-test's error bound)
+    fp.ray4 = fp.fast && (a.S & 3) == 0;
+    fp.use_d1 = fp.ray4 && !a.z_vals;
+    fp.vc_gx = voxel_class_grid(v);
+    return fp;
+}
+
+int launch_front_scene(const RenderArgs& a, const Workspace& w, const GridDev& dg, const FrontPlan& fp, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
         INVR_HIP(hipFuncSetAttribute((const void*)k_front_scene, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PREP_LDS_BYTES));
@@ -1184,9 +1181,8 @@ int launch_front_scene(const RenderArgs& a, const Workspace& w, const GridDev& d
     f.s = a.scene; f.ix = w.knn;
     const VolDev& v = a.scene.pbw;
     const int64_t cells = (int64_t)v.dx * v.dy * v.dz;
-    *have_cells = !(cells > CULL_MASK_MAX || cells > VOXMASK_MAX_CELLS);
     f.thresh_hi = a.scene.thresh * (1.0f + 1e-5f); f.cullmask = w.cullmask; f.n_live = w.counters + CNT_LIVE;
-    f.n_cells_wg = *have_cells ? (int)cdiv(cells, PREP_T) : 0;
+    f.n_cells_wg = fp.have_cells ? (int)cdiv(cells, PREP_T) : 0;
     f.vmat_m = a.scene.M < w.knn.mpad ? a.scene.M : w.knn.mpad;
     f.n_vmat_wg = (int)cdiv(f.vmat_m, PREP_T);
     f.dg = dg; f.dslice = w.dslice;
@@ -1224,20 +1220,15 @@ __global__ __launch_bounds__(CULL_BLOCK) void k_front_cull(RenderArgs a, Workspa
     cull_flag_body<true, FAST, RAY4>(a, w, inv_S, lin_step, (int64_t)(b - vc_gx * INVR_NUM_PARTS));
 }
 
-// lattice classes + cull flags in one launch; returns 0 and sets *done = 0 when the frame does not take the masked cull
-// (launch_cull's condition), in which case the caller runs launch_cull alone
-int launch_front_cull(const RenderArgs& a, const Workspace& w, int* done, hipStream_t st) {
+// lattice classes + cull flags in one launch, for the frames that take the masked cull (fp.masked)
+int launch_front_cull(const RenderArgs& a, const Workspace& w, const FrontPlan& fp, hipStream_t st) {
     const VolDev& v = a.scene.pbw;
     const int64_t cells = (int64_t)v.dx * v.dy * v.dz, nb = cdiv(a.N, CULL_TILE);
-    *done = 0;
-    if (!(a.N >= 4 * cells)) return 0;
-    const unsigned gx = voxel_class_grid(v);
+    const unsigned gx = fp.vc_gx;
     const double inv_S = 1.0 / (double)a.S;
     const float lin_step = 1.0f / (float)(a.S - 1);
-    const bool fast = !a.wpts && !a.jitter && a.N < (1ll << 31) && cells * v.c < (1ll << 31) && a.S >= 2 &&
-                      v.dx <= 1024 && v.dy <= 1024 && v.dz <= 1024;      // (front_bodies.h: the pre-test's error bound)
     const unsigned grid = gx * INVR_NUM_PARTS + (unsigned)nb;
-    if (fast && (a.S & 3) == 0 && !a.z_vals) {
+    if (fp.use_d1) {
         // the cell mask dilated by one cell (k_dilate_mask, ~3 us between the two front launches): a thread of the RAY4 cull drops
         // its four samples on ONE look-up when the whole segment provably stays inside dead cells (front_bodies.h)
         Workspace w2 = w;
@@ -1245,12 +1236,10 @@ int launch_front_cull(const RenderArgs& a, const Workspace& w, int* done, hipStr
         hipLaunchKernelGGL(k_dilate_mask, dim3((unsigned)cdiv(cells, 256)), dim3(256), 0, st, v.dx, v.dy, v.dz, w.cullmask, w.cullmask_d1);
         INVR_LAUNCH_CHECK();
         hipLaunchKernelGGL((k_front_cull<true, true>), dim3(grid), dim3(CULL_BLOCK), 0, st, a, w2, inv_S, lin_step, (int)gx);
-    } else
-    if (fast && (a.S & 3) == 0) hipLaunchKernelGGL((k_front_cull<true, true>), dim3(grid), dim3(CULL_BLOCK), 0, st, a, w, inv_S, lin_step, (int)gx);
-    else if (fast) hipLaunchKernelGGL((k_front_cull<true, false>), dim3(grid), dim3(CULL_BLOCK), 0, st, a, w, inv_S, lin_step, (int)gx);
+    } else if (fp.ray4) hipLaunchKernelGGL((k_front_cull<true, true>), dim3(grid), dim3(CULL_BLOCK), 0, st, a, w, inv_S, lin_step, (int)gx);
+    else if (fp.fast) hipLaunchKernelGGL((k_front_cull<true, false>), dim3(grid), dim3(CULL_BLOCK), 0, st, a, w, inv_S, lin_step, (int)gx);
     else hipLaunchKernelGGL((k_front_cull<false, false>), dim3(grid), dim3(CULL_BLOCK), 0, st, a, w, inv_S, lin_step, (int)gx);
     INVR_LAUNCH_CHECK();
-    *done = 1;
     return 0;
 }
 

@@ -696,21 +696,20 @@ __global__ __launch_bounds__(MLP_BLOCK, RGB_WPS) void k_part_rgb_all(MlpAllArgs 
     }
 }
 
-static bool part_mlp_supported(const PartMlpDev& pm) {
+bool part_mlp_supported(const PartMlpDev& pm) {
     const MlpDev& o = pm.occ;
     const MlpDev& r = pm.rgb;
-    return o.n_linear == 2 && o.dims[0] == 19 && o.dims[1] == HID && o.dims[2] == 17 &&
-           (r.n_linear == 2 || r.n_linear == 3) && r.dims[0] == 70 && r.dims[1] == HID &&
-           r.dims[r.n_linear] == 3 && (r.n_linear == 2 || r.dims[2] == HID) &&
-           pm.n_freq == 4 && pm.latent_dim == 8 && pm.geo_dim == 16;
+    const bool ok = o.n_linear == 2 && o.dims[0] == 19 && o.dims[1] == HID && o.dims[2] == 17 &&
+                    (r.n_linear == 2 || r.n_linear == 3) && r.dims[0] == 70 && r.dims[1] == HID &&
+                    r.dims[r.n_linear] == 3 && (r.n_linear == 2 || r.dims[2] == HID) &&
+                    pm.n_freq == 4 && pm.latent_dim == 8 && pm.geo_dim == 16;
+    if (!ok) invr_set_error("part MLP kernel supports occ 19-64-17 and rgb 70-64(-64)-3 with 4 view-dir frequencies, latent 8, geo feature 16");
+    return ok;
 }
 
 int launch_part_mlp_all(const MlpAllArgs& a, const Workspace& w, hipStream_t st) {
     for (int p = 0; p < INVR_NUM_PARTS; ++p)
-        if (!part_mlp_supported(a.pm[p])) {
-            invr_set_error("part MLP kernel supports occ 19-64-17 and rgb 70-64(-64)-3 with 4 view-dir frequencies, latent 8, geo feature 16");
-            return 1;
-        }
+        if (!part_mlp_supported(a.pm[p])) return 1;
     const int64_t per_block = (MLP_BLOCK / 64) * MLP_CB * 16;
     int64_t tiles = cdiv(a.cap, per_block);
     unsigned grid_occ = (unsigned)(tiles < 256 * 4 ? (tiles > 0 ? tiles : 1) : 256 * 4);
@@ -740,20 +739,11 @@ int launch_part_mlp_all(const MlpAllArgs& a, const Workspace& w, hipStream_t st)
 #define MLP_WPS 3          // workgroups per CU the single-part kernel is launched for
 int launch_part_mlp(const PartMlpDev& pm, const float* emb, const float* d_soa, int64_t stride,
                     const int32_t* count, int64_t cap, float4* raw_direct, hipStream_t st) {
-    const MlpDev& o = pm.occ;
-    const MlpDev& r = pm.rgb;
-    bool ok = o.n_linear == 2 && o.dims[0] == 19 && o.dims[1] == HID && o.dims[2] == 17 &&
-              (r.n_linear == 2 || r.n_linear == 3) && r.dims[0] == 70 && r.dims[1] == HID &&
-              r.dims[r.n_linear] == 3 && (r.n_linear == 2 || r.dims[2] == HID) &&
-              pm.n_freq == 4 && pm.latent_dim == 8 && pm.geo_dim == 16;
-    if (!ok) {
-        invr_set_error("part MLP kernel supports occ 19-64-17 and rgb 70-64(-64)-3 with 4 view-dir frequencies, latent 8, geo feature 16");
-        return 1;
-    }
+    if (!part_mlp_supported(pm)) return 1;
     const int64_t per_block = (MLP_BLOCK / 64) * MLP_CB * 16;
     int64_t tiles = cdiv(cap, per_block);
     unsigned grid = (unsigned)(tiles < 256 * MLP_WPS ? (tiles > 0 ? tiles : 1) : 256 * MLP_WPS);
-    if (r.n_linear == 3)
+    if (pm.rgb.n_linear == 3)
         hipLaunchKernelGGL(k_part_mlp<3>, dim3(grid), dim3(MLP_BLOCK), 0, st, pm, emb, d_soa, stride, count, cap, raw_direct);
     else
         hipLaunchKernelGGL(k_part_mlp<2>, dim3(grid), dim3(MLP_BLOCK), 0, st, pm, emb, d_soa, stride, count, cap, raw_direct);

@@ -133,24 +133,11 @@ int launch_warp_deform_dense(const SceneDev& s, const GridDev& dg, const MlpDev&
 // Two kernels so that neither carries the other's live state (LBS: 24 blend weights + two 3x4
 // matrices; deformer: 19 features + two 32-wide hidden layers): each fits well under 128 VGPRs and
 // runs at >= 4 waves/SIMD instead of the 2 waves/SIMD (256 VGPRs) of the fused form.
-// Per-vertex pre-blended matrices (built once per frame, k_vertex_mats): bw @ A with bw = sum_k w_k pbw[nn_k]
+// Per-vertex pre-blended matrices (built once per frame, vertex_mats_body in k_front_scene): bw @ A with bw = sum_k w_k pbw[nn_k]
 // is linear in the skinning rows, so  A_bw = sum_k w_k M_A[nn_k]  with  M_A[v] = sum_j pbw[v][j] A_j  (and the same
 // for big_A).  A pair then needs 4 x 96 B gathers and 96 FMAs instead of 4 x 96 B gathers, the 24-wide blend and
 // 576 FMAs against 576 scalar matrix entries (which the compiler could only keep by spilling SGPRs into VGPR
 // lanes: 2.2 k v_readlane / v_writelane per pair made the old kernel VALU-bound at 0.32 ms).
-__global__ __launch_bounds__(VMAT_BLOCK) void k_vertex_mats(SceneDev s, KnnIndex ix, const float* __restrict__ A,
-                                                           const float* __restrict__ big_A) {
-    vertex_mats_body(s, ix, A, big_A, (int)blockIdx.y, (int)(blockIdx.x * VMAT_BLOCK + threadIdx.x));
-}
-
-int launch_vertex_mats(const RenderArgs& a, const Workspace& w, hipStream_t st) {
-    const int m = a.scene.M < w.knn.mpad ? a.scene.M : w.knn.mpad;
-    hipLaunchKernelGGL(k_vertex_mats, dim3((unsigned)cdiv(m, VMAT_BLOCK), INVR_NUM_PARTS), dim3(VMAT_BLOCK), 0, st, a.scene, w.knn,
-                       a.scene.A, a.scene.big_A);
-    INVR_LAUNCH_CHECK();
-    return 0;
-}
-
 // canonical point / direction of pair i of part p's list
 __device__ __forceinline__ void warp_pair(const RenderArgs& a, const Workspace& w, const float4* __restrict__ vm, const int p, const int64_t i,
                                           float* xb, float* db) {
@@ -391,12 +378,8 @@ __global__ __launch_bounds__(DF_BLOCK) void k_deform_pairs(RenderArgs a, Workspa
 // So per level the z corner pair and its weight are the same for every point, and the 3-D grid collapses
 // to a 2-D (u,v) table  S_l[cx][cy] = (1-tz) row(cx,cy,c0z) + tz row(cx,cy,c1z)  (hashed levels included:
 // the slice of a hashed level is materialised densely).  sum_l res_l^2 = 2959 entries (24 KB) for the
-// reference's 8 levels — built once per call by k_deform_slice and held in LDS, so the 64 L1-line gathers
+// reference's 8 levels — built once per call by deform_slice_body (k_front_scene) and held in LDS, so the 64 L1-line gathers
 // per pair that bounded the kernel become 32 ds_read_b64.  (u,v) index math stays the reference's.
-__global__ void k_deform_slice(GridDev dg, DfSliceInfo si, const float* __restrict__ frame_dim, float2* __restrict__ out) {
-    deform_slice_body(dg, si, frame_dim, out, (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
-
 struct LaneSlice { int off, res; float cell; };
 
 __device__ __forceinline__ void lane_level_slice(const float2* S, const LaneSlice& L, float x, float y, float& f0, float& f1) {
@@ -552,15 +535,6 @@ __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(DF_WPE
     }
 }
 
-// depends on the grid and frame_dim only (not on the pair lists): launched on the side stream beside the KNN
-int launch_deform_slice(const RenderArgs& a, const Workspace& w, const GridDev& dg, hipStream_t st) {
-    DfSliceInfo si;
-    if (!deform_slices_fit(dg, si)) return 0;
-    hipLaunchKernelGGL(k_deform_slice, dim3((unsigned)cdiv(si.off[8], 256)), dim3(256), 0, st, dg, si, a.scene.frame_dim, w.dslice);
-    INVR_LAUNCH_CHECK();
-    return 0;
-}
-
 // ---- backward of the deformer's grid through the same t-slices -------------------------------------------------------------
 // feature (l, f) of a point = sum over its four (u, v) corners of w_uv * S_l[corner][f],  S_l = (1-tz) row(., ., c0z) + tz row(., ., c1z)
 // with ONE tz per call.  So the table gradient is the transposed two-step: every workgroup scatter-adds w_uv * g into a 24 KB LDS
@@ -657,7 +631,7 @@ int launch_warp_pairs(const RenderArgs& a, const Workspace& w, const GridDev& dg
     int64_t dtiles = cdiv(w.lcap, DF_BLOCK);
     unsigned dgx = (unsigned)(dtiles < 512 ? (dtiles > 0 ? dtiles : 1) : 512);
     DfSliceInfo si;
-    if (deform_slices_fit(dg, si)) {                 // slices built by launch_deform_slice
+    if (deform_slices_fit(dg, si)) {                 // slices built by k_front_scene
         const size_t lds_bytes = (size_t)DF_LDS * sizeof(float) + (size_t)si.off[8] * sizeof(float2);
         auto kern = volume_is_small(a.scene.tuv) ? k_deform_pairs_slice<true> : k_deform_pairs_slice<false>;
         hipLaunchKernelGGL(kern, dim3(dgx, INVR_NUM_PARTS), dim3(DF_BLOCK), lds_bytes, st, a, w, dg, si, dm.w[0], dm.b[0],

@@ -28,7 +28,7 @@ struct RenderArgs {
     int64_t N;               // R*S
 };
 
-// per-frame KNN acceleration index built by k_part_prepare
+// per-frame KNN acceleration index built by part_prepare_body (k_front_scene)
 struct KnnIndex {
     float4* sverts;      // P*mpad : Morton-sorted vertices, two per float4 pair: {x0,x1,y0,y1} {z0,z1,|v0|^2,|v1|^2}
     uint16_t* srow;      // P*mpad : row of every sorted vertex slot inside its part (0 for the padding sentinels)
@@ -37,12 +37,12 @@ struct KnnIndex {
                          //            bound of the nearest distance)}
     float* part_aabb;    // P*6
     float* dfar2;        // 1 : squared distance beyond which a (point, part) pair is folded into the part's far constant, derived per
-                         //     frame from the magnitude of A / big_A (k_part_prepare)
+                         //     frame from the magnitude of A / big_A (part_prepare_body)
     unsigned long long* voxmask;  // per lattice cell and part: bit c set if cluster c can hold one of the 4 nearest vertices of a
                          //            point of the cell (undecided cells of parts with <= 64 clusters; all ones otherwise); NULL = off
     float* voxu2;        // per (lattice cell, part): squared upper bound of the 4th-nearest distance of any point of the cell
     uint8_t* voxcls;     // per (lattice cell, part): 0 never classified (mask / bound stale), 1 far, 2 unflagged, 3 undecided; NULL = off
-    int32_t* live_cells; // lattice cells with a corner below the cull threshold (k_cull_cells; count in counters[CNT_LIVE])
+    int32_t* live_cells; // lattice cells with a corner below the cull threshold (cull_cells_body; count in counters[CNT_LIVE])
     float4* vmat;        // P*mpad*6 : per vertex, rows 0..2 of sum_j pbw[v][j] A_j and of sum_j pbw[v][j] big_A_j
     int32_t mpad, cpad;
 };
@@ -141,17 +141,23 @@ __device__ __forceinline__ void sample_pose_point(const RenderArgs& a, int64_t i
 }
 
 // ---- pipeline stage launchers ------------------------------------------------------------------
-int launch_cull_cells(const RenderArgs& a, const Workspace& w, hipStream_t st);      // -> 1 if the cell mask / live list were built
-int launch_cull(const RenderArgs& a, const Workspace& w, int64_t max_active, bool have_cells, bool flags_done, hipStream_t st);   // flags_done: k_front_cull wrote the masks, only scan + compaction remain
-int launch_front_scene(const RenderArgs& a, const Workspace& w, const GridDev& dg, int* have_cells, hipStream_t st);     // k_knn.hip: index + cell mask + vertex matrices + deformer slices, one launch
-int launch_front_cull(const RenderArgs& a, const Workspace& w, int* done, hipStream_t st);                               // k_knn.hip: lattice-cell classes + cull flags, one launch
+// How the front of this frame runs, decided ONCE per frame (plan_front, k_knn.hip) and read by the three front launchers.
+struct FrontPlan {
+    bool have_cells;     // the distance volume's lattice fits the cell mask / class tables: k_front_scene builds the mask and the live-cell list
+    bool masked;         // have_cells and the mask pays for itself (N >= 4 cells: full frames): k_front_cull writes the cull flags beside the cell classes
+    bool fast;           // masked cull with the one-multiply cell pre-test (front_bodies.h: its error bound)
+    bool ray4;           // fast, four consecutive samples of one ray per thread (S % 4 == 0)
+    bool use_d1;         // ray4 without z_vals: segments are dropped on one look-up of the dilated mask (k_dilate_mask)
+    unsigned vc_gx;      // workgroups per part of the lattice-cell classification
+};
+FrontPlan plan_front(const RenderArgs& a);
+int launch_front_scene(const RenderArgs& a, const Workspace& w, const GridDev& dg, const FrontPlan& fp, hipStream_t st);   // k_knn.hip: index + cell mask + vertex matrices + deformer slices, one launch
+int launch_front_cull(const RenderArgs& a, const Workspace& w, const FrontPlan& fp, hipStream_t st);      // k_knn.hip, fp.masked frames: lattice-cell classes + cull flags, one launch
+int launch_cull(const RenderArgs& a, const Workspace& w, int64_t max_active, const FrontPlan& fp, hipStream_t st);      // unmasked cull flags unless fp.masked, then scan + compaction
 int launch_pose_points(const RenderArgs& a, const int32_t* idx, int64_t n, float* pts, float* dirs, hipStream_t st);
-int launch_knn_prepare(const RenderArgs& a, const Workspace& w, hipStream_t st);
-int launch_vertex_mats(const RenderArgs& a, const Workspace& w, hipStream_t st);
 int launch_knn_voxel_class(const RenderArgs& a, const Workspace& w, hipStream_t st);
 int launch_knn_pairs(const RenderArgs& a, const Workspace& w, int32_t* stats, hipStream_t st);     // stats: exported behind the pair lists when given
 int launch_knn_pdist(const RenderArgs& a, const Workspace& w, hipStream_t st);      // aggr 'dist' / 'mindist': part_dist of all (survivor, part)
-int launch_deform_slice(const RenderArgs& a, const Workspace& w, const GridDev& dg, hipStream_t st);   // per-call t-slices of the deformer grid (no-op when they do not fit)
 int launch_warp_pairs(const RenderArgs& a, const Workspace& w, const GridDev& dg, const MlpDev& dm, hipStream_t st);
 int launch_part_encode(const GridDev& g, const float* x_soa, int64_t stride, const int32_t* count, int64_t cap,
                        float* emb, hipStream_t st);
@@ -170,6 +176,9 @@ struct PartMlpDev {
     const int64_t* latent_index;
     int32_t latent_dim, n_freq, geo_dim;
 };
+// The one shape rule of every part-MLP kernel, forward and backward (they stage weights through the same stage_weights<NRGB>,
+// mlp_common.h, which reads a 64 x 64 middle layer of a three-linear colour MLP); sets the error text when it fails
+bool part_mlp_supported(const PartMlpDev& pm);
 int launch_part_mlp(const PartMlpDev& pm, const float* emb, const float* d_soa, int64_t stride,
                     const int32_t* count, int64_t cap, float4* raw_direct, hipStream_t st);
 struct MlpBwdOut {                 // k_mlp_bwd.hip; mirrors InvrMlpBwdOut

@@ -14,6 +14,35 @@ def declared_symbols():
     return sorted(set(re.findall(r'\b(invr_[a-z_0-9]+)\s*\(', src)))
 
 
+def header_prototypes():
+    """-> [(return type, name, [parameter declarations])] of every function include/invr.h declares, in its order."""
+    src = open(os.path.join(ROOT, 'include', 'invr.h')).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    src = re.sub(r'//[^\n]*', '', src)
+    protos = re.findall(r'^[ \t]*((?:const\s+)?[A-Za-z_0-9]+\s*\*?)\s*(invr_[a-z_0-9]+)\s*\(([^;{)]*)\)\s*;', src, flags=re.M)
+    return [(ret.strip(), name, [a.strip() for a in args.split(',') if a.strip() != 'void']) for ret, name, args in protos]
+
+
+def c_kind(decl):
+    """Class of a C return type / parameter declaration: 'ptr', or (kind, bytes) with kind 'int' / 'uint' / 'float'."""
+    import ctypes as C
+    if '*' in decl or '[' in decl:
+        return 'ptr'
+    base = re.sub(r'\bconst\b', '', decl).split()[0]
+    return {'int': ('int', C.sizeof(C.c_int)), 'int32_t': ('int', 4), 'int64_t': ('int', 8), 'uint8_t': ('uint', 1), 'uint32_t': ('uint', 4),
+            'uint64_t': ('uint', 8), 'size_t': ('uint', C.sizeof(C.c_size_t)), 'float': ('float', 4), 'double': ('float', 8)}[base]
+
+
+def ctypes_kind(t):
+    """The same class of a ctypes type, by kind and sizeof (c_int32 is c_int and c_size_t is c_ulong on this ABI)."""
+    import ctypes as C
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, (C._Pointer, C.Array)):
+        return 'ptr'
+    code = t._type_
+    assert code in 'bhilqBHILQfd', t
+    return ('float' if code in 'fd' else 'int' if code.islower() else 'uint', C.sizeof(t))
+
+
 def test_library_exports_header_symbols():
     from invr import _abi
     if not os.path.exists(_abi.LIB_PATH):
@@ -29,6 +58,65 @@ def test_library_exports_header_symbols():
     import re
     hdr = open(os.path.join(ROOT, 'include', 'invr.h')).read()
     assert int(re.search(r'#define INVR_ABI_VERSION (\d+)', hdr).group(1)) == _abi.ABI_VERSION
+    # every declaration parses as a prototype, and the binding's one table states each with the header's types, in the header's order
+    protos = header_prototypes()
+    assert len(protos) == 50
+    assert sorted(name for _, name, _ in protos) == names, 'an invr_ declaration of the header did not parse as a prototype'
+    assert [name for _, name, _ in protos] == list(_abi.SIGNATURES) == _abi.EXPORTS
+    for ret, name, params in protos:
+        restype, argtypes = _abi.SIGNATURES[name]
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name          # lib() applied the table
+        assert ctypes_kind(restype) == c_kind(ret), (name, 'return type', ret, restype)
+        assert len(argtypes) == len(params), (name, params, argtypes)
+        for i, (decl, t) in enumerate(zip(params, argtypes)):
+            assert ctypes_kind(t) == c_kind(decl), (name, i, decl, t)
+
+
+def test_signature_classes_tell_widths_apart():
+    """The comparison above is by kind and size: a 32-bit type where the header says int64_t, or a float for a double, is a mismatch."""
+    import ctypes as C
+    assert ctypes_kind(C.c_int32) == c_kind('int32_t which') == c_kind('int') != c_kind('int64_t n')
+    assert ctypes_kind(C.c_int64) == c_kind('int64_t n') != ctypes_kind(C.c_uint64) == c_kind('size_t workspace_bytes')
+    assert ctypes_kind(C.c_float) == c_kind('float eps') != ctypes_kind(C.c_double) == c_kind('double beta1')
+    assert ctypes_kind(C.c_int32 * 3) == c_kind('const int32_t dims[3]') == c_kind('float* const* dW') == ctypes_kind(C.POINTER(C.c_void_p)) == 'ptr'
+    assert ctypes_kind(C.c_char_p) == c_kind('const char*') == 'ptr'
+
+
+def default_model():
+    """An InvrModel with the default layer shapes (occ 19-64-17, rgb 70-64-64-3) and no tables or weights: for calls that must stop
+    at an argument check."""
+    from invr import _abi
+    m = _abi.InvrModel()
+    for p in range(_abi.NUM_PARTS):
+        part = m.part[p]
+        part.occ.n_linear, part.rgb.n_linear = 2, 3
+        part.occ.dims[:3] = [19, 64, 17]
+        part.rgb.dims[:4] = [70, 64, 64, 3]
+        part.latent_dim, part.num_latent_code = 8, 1
+    m.n_dir_freq, m.geo_feature_dim = 4, 16
+    return m
+
+
+def test_part_mlp_backward_refuses_what_the_forward_refuses():
+    """One shape rule for the part MLPs: a 70-64-32-3 colour MLP (the kernels stage a 64 x 64 middle layer) is refused by the stand-alone
+    backward entry points with the forward's message, ahead of the data-pointer checks — nothing is launched."""
+    import ctypes as C
+    from invr import _abi
+    L = _abi.lib()
+    li = (C.c_int64 * 1)(0)
+    out = _abi.InvrMlpBwdOut()
+    cnt = (C.c_int32 * 1)(4)
+
+    def calls(m):
+        yield L.invr_part_mlp_bwd(C.byref(m), 0, li, None, None, 4, None, C.byref(out), None)
+        yield L.invr_part_mlp_bwd_lists(C.byref(m), 0, li, None, None, 4, 4, cnt, None, None, C.byref(out), 0, None)
+    m = default_model()
+    for st in calls(m):          # the default shapes pass the rule: the call stops at its NULL data pointers
+        assert st != 0 and b'null pointer' in L.invr_last_error(), L.invr_last_error()
+    m.part[0].rgb.dims[2] = 32
+    for st in calls(m):
+        assert st != 0 and b'part MLP kernel supports occ 19-64-17 and rgb 70-64(-64)-3' in L.invr_last_error(), L.invr_last_error()
 
 
 def test_workspace_query_and_error_path():

@@ -1073,7 +1073,7 @@ def test_render_other_scenes_vs_oracle(scene_kw):
 @pytest.mark.parametrize('scale', [1.0, 40.0, float('nan')], ids=['as-is', 'x40', 'nan'])
 def test_far_fold_distance_follows_the_frame_matrices(gpu_setup, scale):
     """Far-constant folding (k_knn.hip header) rests on |A_bw| <= s * max|A| being below fp32 resolution; the distance beyond
-    which a (survivor, part) pair is folded is derived per frame from the largest |entry| of A / big_A (k_part_prepare ->
+    which a (survivor, part) pair is folded is derived per frame from the largest |entry| of A / big_A (part_prepare_body ->
     ix.dfar2): (0.68 m)^2 while that is <= 2, larger beyond, +inf (no folding) for non-finite matrices.  What the fold claims is
     then checked directly: the dense warp (invr_knn_blend + invr_warp_deform, the reference's arithmetic for every pair) puts
     every folded pair's canonical point within 1.5e-8 m of the origin with a view direction below 1e-15."""

@@ -56,5 +56,5 @@ for i, n in enumerate(names):
 print('total per wave-tile %.0f cycles (s_memtime ticks: 100 MHz constant clock on gfx9 -> x10 ns)' % (tot / tiles))
 
 n = max(v[16 + 8], 1)
-print('k_part_prepare (workgroup 0 = part 0), cycles per launch: AABB %.0f  keys %.0f  sort %.0f  vertex write %.0f  cluster records %.0f'
+print('part_prepare_body (workgroup 0 of k_front_scene = part 0), cycles per launch: AABB %.0f  keys %.0f  sort %.0f  vertex write %.0f  cluster records %.0f'
       % tuple(v[16 + i] / n for i in range(5)))
