@@ -84,6 +84,13 @@ class InvrWsLayout(C.Structure):
                 ('byte_off', C.c_int64)]
 
 
+class InvrPerceptualLayout(C.Structure):
+    """include/invr_perceptual.h: byte offsets of every intermediate of the perceptual loss in the caller's workspace."""
+    ARRAYS = ('rank', 'img', 'a11', 'a12', 'pool', 'a21', 'a22', 'partial', 'out8', 'g22', 'gm22', 'g21', 'gm21', 'gpool', 'g12', 'gm12',
+              'g11', 'gm11', 'gimg')
+    _fields_ = [(k, C.c_int64) for k in ARRAYS + ('n_part1', 'n_part2', 'n_partial', 'bytes')]
+
+
 def _signatures():
     """name -> (restype, argtypes) of every prototype of include/invr.h, in the header's order (tests/test_abi_symbols.py holds each
     entry against the header's text).  vp = any data pointer: device tensors, host arrays and the stream go through as addresses."""
@@ -146,7 +153,24 @@ def _signatures():
     }
 
 
+def _signatures_perceptual():
+    """The same table for include/invr_perceptual.h (tests/test_abi_perceptual_cpu.py holds it against that header's text)."""
+    i32, i64, f32, size, vp = C.c_int32, C.c_int64, C.c_float, C.c_size_t, C.c_void_p
+    ws = [vp, size]                                # workspace, workspace_bytes
+    return {
+        'invr_perceptual_packed_floats': (i64, ()),
+        'invr_perceptual_pack_weights': (C.c_int, [C.POINTER(vp), C.POINTER(vp), vp, vp]),
+        'invr_perceptual_workspace_bytes': (size, [i32, i32]),
+        'invr_perceptual_workspace_layout': (C.c_int, [i32, i32, C.POINTER(InvrPerceptualLayout)]),
+        'invr_perceptual_fwd': (C.c_int, [vp, vp, vp, vp, i64, i32, i32] + ws + [vp, vp]),
+        'invr_perceptual_bwd': (C.c_int, [vp, vp, i64, i32, i32] + ws + [vp, vp, vp]),
+        'invr_train_loss_lpips_fwd': (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, i32] + ws + [vp, vp, vp]),
+        'invr_train_loss_lpips_bwd': (C.c_int, [vp, vp, vp, i64, i32, i32, f32, f32, f32, i32] + ws + [vp, vp, vp, vp, vp]),
+    }
+
+
 SIGNATURES = _signatures()
+SIGNATURES_PERCEPTUAL = _signatures_perceptual()
 EXPORTS = list(SIGNATURES)
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
 BWD_HEAD, BWD_DEFORMER, BWD_ALL = 1, 64, 127
@@ -164,7 +188,7 @@ def lib():
             raise RuntimeError('libinvr.so is not built (%s); run `python -c "import __graft_entry__ as g; g.build()"`. '
                                'There is no CPU fallback for the render path.' % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
+        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
         if L.invr_version() != ABI_VERSION:
@@ -227,6 +251,45 @@ def ws_views(ws, n_rays, S, max_active, n_active=None):
     v['l_w'] = [view(lay.l_w[p], 4 * lc, torch.float32).view(lc, 4) for p in range(NUM_PARTS)]       # normalised gaussian weights
     v['emb'] = [view(lay.emb[p], 20 * lc, torch.float32).view(20, lc) for p in range(NUM_PARTS)]      # encoder outputs, SoA [k][pair]
     return v
+
+
+def perceptual_views(ws, H, W):
+    """Zero-copy tensor views of every array invr_perceptual_fwd / _bwd keep in the workspace `ws` (uint8 tensor): the assembled images,
+    the stored activations of both images, the per-wave partial sums and the gradient arriving at each layer's output."""
+    lay = InvrPerceptualLayout()
+    check(lib().invr_perceptual_workspace_layout(H, W, C.byref(lay)))
+    P, h, w = H * W, H // 2, W // 2
+
+    def view(off, shape, dtype=torch.float32):
+        count = 1
+        for d in shape:
+            count *= d
+        return ws[off:off + count * torch.empty((), dtype=dtype).element_size()].view(dtype).view(*shape)
+    v = {'layout': lay, 'rank': view(lay.rank, (H, W), torch.int32), 'img': view(lay.img, (2, 3, H, W)),
+         'a11': view(lay.a11, (2, 64, H, W)), 'a12': view(lay.a12, (2, 64, H, W)), 'pool': view(lay.pool, (2, 64, h, w)),
+         'a21': view(lay.a21, (2, 128, h, w)), 'a22': view(lay.a22, (2, 128, h, w)),
+         'partial': view(lay.partial, (lay.n_partial,), torch.float64), 'out8': view(lay.out8, (8,)),
+         'gpool': view(lay.gpool, (64, h, w)), 'gimg': view(lay.gimg, (3, H, W))}
+    for k in ('g22', 'gm22', 'g21', 'gm21'):
+        v[k] = view(getattr(lay, k), (128, h, w))
+    for k in ('g12', 'gm12', 'g11', 'gm11'):
+        v[k] = view(getattr(lay, k), (64, H, W))
+    return v
+
+
+def perceptual_pack(weights, biases, packed=None):
+    """The packed weight image of invr_perceptual_pack_weights from the four (out, in, 3, 3) weights and (out) biases (device tensors)."""
+    L = lib()
+    ws = [_f32c(t) for t in weights]
+    bs = [_f32c(t) for t in biases]
+    assert [tuple(t.shape) for t in ws] == [(64, 3, 3, 3), (64, 64, 3, 3), (128, 64, 3, 3), (128, 128, 3, 3)], [tuple(t.shape) for t in ws]
+    assert [tuple(t.shape) for t in bs] == [(64,), (64,), (128,), (128,)]
+    if packed is None:
+        packed = torch.empty(L.invr_perceptual_packed_floats(), device=ws[0].device)
+    wp = (C.c_void_p * 4)(*[ptr(t).value for t in ws])
+    bp = (C.c_void_p * 4)(*[ptr(t).value for t in bs])
+    check(L.invr_perceptual_pack_weights(wp, bp, ptr(packed), stream_ptr()))
+    return packed
 
 
 def stream_ptr():

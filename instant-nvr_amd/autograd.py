@@ -619,6 +619,49 @@ class TrainLossFn(torch.autograd.Function):
         return g_rgb, None, g_dist, g_terms, None, None, None, None
 
 
+class TrainLossPerceptualFn(torch.autograd.Function):
+    """TrainLossFn's twin for cfg.use_lpips (invr_train_loss_lpips_fwd / _bwd, include/invr_perceptual.h): the regulariser terms as
+    there and, in the place of the MSE in the sum, the perceptual loss of the patch re-assembled from mask_at_box (uint8, H*W) — VGG
+    forward for both images, backward to rgb_map, every intermediate in the caller's workspace `ws`.  -> (out8 = [loss, img_loss,
+    psnr, reg_dist, offset_loss, pair_loss, lpips_loss, 0], err (n,)); only out8[0] carries a gradient, the MSE and psnr are
+    statistics."""
+
+    @staticmethod
+    def forward(ctx, rgb, gt, dist, terms, packed, mask, ws, H, W, w_pair, w_dist, w_off, use_pair, owner=None):
+        L = _abi.lib()
+        rgb, gt = rgb.contiguous(), gt.contiguous().to(torch.float32)
+        n = rgb.shape[0]
+        out = torch.empty(8, device=rgb.device)
+        err = torch.empty(n, device=rgb.device)
+        dist_c = dist.contiguous() if dist is not None else None
+        _abi.check(L.invr_train_loss_lpips_fwd(_abi.ptr(packed), _abi.ptr(rgb), _abi.ptr(gt), _abi.ptr(mask, torch.uint8), _abi.ptr(dist_c),
+                                               _abi.ptr(terms), n, H, W, w_pair, w_dist, w_off, int(use_pair), _abi.ptr(ws, torch.uint8),
+                                               ws.numel(), _abi.ptr(out), _abi.ptr(err), _abi.stream_ptr()))
+        ctx.save_for_backward(terms, packed, mask, ws)
+        ctx.has_dist, ctx.n, ctx.args = dist is not None, n, (H, W, w_pair, w_dist, w_off, int(use_pair))
+        ctx.owner, ctx.gen = owner, getattr(owner, 'gen', None)      # (the workspace's owner counts its hand-outs)
+        ctx.mark_non_differentiable(err)
+        return out, err
+
+    @staticmethod
+    def backward(ctx, g_out, _g_err):
+        L = _abi.lib()
+        terms, packed, mask, ws = ctx.saved_tensors
+        if getattr(ctx.owner, 'gen', None) != ctx.gen:
+            raise RuntimeError('TrainLossPerceptualFn.backward: the perceptual workspace was handed to a later forward before this '
+                               'backward ran; its intermediates are gone (run backward before the next iteration\'s forward)')
+        n = ctx.n
+        g_loss = g_out[:1].contiguous()
+        g_rgb = torch.empty(n, 3, device=terms.device)
+        g_dist = torch.empty(n, device=terms.device) if ctx.has_dist else None
+        g_terms = torch.empty(TERM_LEN, device=terms.device)
+        H, W, w_pair, w_dist, w_off, use_pair = ctx.args
+        _abi.check(L.invr_train_loss_lpips_bwd(_abi.ptr(packed), _abi.ptr(mask, torch.uint8), _abi.ptr(terms), n, H, W, w_pair, w_dist, w_off,
+                                               use_pair, _abi.ptr(ws, torch.uint8), ws.numel(), _abi.ptr(g_loss), _abi.ptr(g_rgb),
+                                               _abi.ptr(g_dist), _abi.ptr(g_terms), _abi.stream_ptr()))
+        return (g_rgb, None, g_dist, g_terms) + (None,) * 10
+
+
 class LazyTrainRet(dict):
     """The train-mode return dict of Renderer.render.  rgb_map / acc_map / raw / occ / reg_distortion_loss and the fused
     regulariser terms (offset_loss, pair_loss: differentiable scalars) are present; the reference's dynamic-shape tensors

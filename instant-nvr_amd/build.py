@@ -7,8 +7,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'libinvr.so')
-SOURCES = ['invr_abi.hip', 'k_cull.hip', 'k_knn.hip', 'k_warp.hip', 'k_encode.hip', 'k_mlp.hip', 'k_composite.hip', 'k_rays.hip', 'k_prep.hip', 'k_optim.hip', 'k_mlp_bwd.hip', 'k_train.hip', 'k_metrics.hip']
-HEADERS = ['common.h', 'pipeline.h', 'grid_generic.h', 'mlp_common.h', 'train.h', os.path.join('..', '..', 'include', 'invr.h')]
+SOURCES = ['invr_abi.hip', 'k_cull.hip', 'k_knn.hip', 'k_warp.hip', 'k_encode.hip', 'k_mlp.hip', 'k_composite.hip', 'k_rays.hip', 'k_prep.hip', 'k_optim.hip', 'k_mlp_bwd.hip', 'k_train.hip', 'k_metrics.hip', 'k_perceptual.hip']
+HEADERS = ['common.h', 'pipeline.h', 'grid_generic.h', 'mlp_common.h', 'train.h', os.path.join('..', '..', 'include', 'invr.h'),
+           os.path.join('..', '..', 'include', 'invr_perceptual.h')]
 # -ffp-contract=off: FMAs only where the source says fmaf(), so the discrete decisions of the path
 # (cull / flag thresholds, integer cell selection) see the same fp32 arithmetic as the reference.
 # -fno-slp-vectorize (round 6): no COMPILER-generated packed-fp32 math (v_pk_mul / v_pk_add / v_pk_fma_f32 with op_sel shuffles).  The SLP

@@ -92,18 +92,50 @@ class NetworkWrapper(nn.Module):
                 setattr(self, attr, host(window_size=11) if flag == 'use_ssim' else host())
 
     def _fused_objective(self, ret, batch):
-        """split 'train' on the fused node with the plain MSE image term: the whole objective as ONE autograd node (autograd.TrainLossFn;
-        same terms, same order of additions as the op-by-op form below) -> (loss, scalar_stats) or None when it does not apply."""
+        """split 'train' on the fused node: the whole objective as ONE autograd node, same terms, same order of additions as the
+        op-by-op form below -> (loss, scalar_stats) or None when it does not apply.  The image term is the plain MSE
+        (autograd.TrainLossFn) or, with cfg.use_lpips and a perceptual-loss module that is recognisably the reference's VGG19 prefix
+        (losses.vgg_convs), the perceptual loss on the HIP kernels (autograd.TrainLossPerceptualFn); any other module — an injected
+        stand-in — keeps the op-by-op path."""
         cfg = self.cfg
         last = getattr(self.renderer, 'last_train', None)
         if (last is None or last.get('terms') is None or not cfg.get('train_fused_loss', True)
-                or cfg.get('use_lpips', False) or cfg.get('use_ssim', False) or cfg.get('use_fourier', False) or cfg.get('use_tv_image', False)):
+                or cfg.get('use_ssim', False) or cfg.get('use_fourier', False) or cfg.get('use_tv_image', False)):
             return None
-        from .autograd import TrainLossFn
         dist = ret['reg_distortion_loss'][0] if dict.__contains__(ret, 'reg_distortion_loss') else None
+        if cfg.get('use_lpips', False):
+            return self._fused_perceptual_objective(ret, batch, last, dist)
+        from .autograd import TrainLossFn
         out, err = TrainLossFn.apply(ret['rgb_map'][0], batch['rgb'][0], dist, last['terms'], float(cfg.pair_loss_weight), float(cfg.reg_dist_weight),
                                      float(cfg.resd_loss_weight), bool(cfg.use_pair_reg))
         stats = {'loss': out[0], 'img_loss': out[1].detach(), 'psnr': out[2:3].detach(), 'offset_loss': out[4].detach()}
+        if dist is not None:
+            stats['reg_dist'] = out[3].detach()
+        if cfg.use_pair_reg:
+            stats['pair_loss'] = out[5].detach()
+        ret['error'] = err[None]
+        return out[0], stats
+
+    def _fused_perceptual_objective(self, ret, batch, last, dist):
+        cfg = self.cfg
+        from .losses import FusedPerceptual, vgg_convs
+        convs = vgg_convs(getattr(self, 'perceptual_loss', None)) if cfg.get('fused_perceptual', True) else None
+        rgb = ret['rgb_map'][0]
+        if convs is None or convs[0].weight.device != rgb.device or convs[0].weight.dtype != torch.float32:
+            return None
+        from .autograd import TrainLossPerceptualFn
+        H, W = int(batch['H'].item()), int(batch['W'].item())                           # as the reference reads them (:188-189)
+        if min(H, W) < 2:                                                               # (no pooled unit: the kernels take H, W >= 2)
+            return None
+        if not hasattr(self, '_fused_perceptual'):
+            self._fused_perceptual = FusedPerceptual()
+        fp = self._fused_perceptual
+        mask = batch['mask_at_box'][0].reshape(-1).to(device=rgb.device, dtype=torch.uint8).contiguous()
+        out, err = TrainLossPerceptualFn.apply(rgb, batch['rgb'][0], dist, last['terms'], fp.packed(convs), mask, fp.workspace(H, W, rgb.device),
+                                               H, W, float(cfg.pair_loss_weight), float(cfg.reg_dist_weight), float(cfg.resd_loss_weight),
+                                               bool(cfg.use_pair_reg), fp)
+        stats = {'loss': out[0], 'img_loss': out[1].detach(), 'psnr': out[2:3].detach(), 'offset_loss': out[4].detach(),
+                 'lpips_loss': out[6].detach()}
         if dist is not None:
             stats['reg_dist'] = out[3].detach()
         if cfg.use_pair_reg:

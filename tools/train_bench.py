@@ -1,6 +1,10 @@
 """Training-iteration timing on one MI355X (BASELINE configs[4] shape by default: 1024 rays x 128 samples, full-size model).
   python tools/train_bench.py [--rays-side 32] [--samples 128] [--iters 50] [--graph] [--prof]
-Reports the un-synchronised iteration time (the loop only syncs at the end) and a synchronised fwd / bwd / opt split."""
+Reports the un-synchronised iteration time (the loop only syncs at the end) and a synchronised fwd / bwd / opt split.
+  python tools/train_bench.py --lpips [--iters 50]
+The same iteration with cfg.use_lpips True (the configs/inb/inb_377.yaml default) and a seeded PerceptualLoss(allow_random=True) at a
+64 x 64 and a 56 x 56 patch: cfg.fused_perceptual False (torch ops) against True (csrc/k_perceptual.hip), interleaved in one process,
+then the per-launch device times of the perceptual kernels (profiles/perceptual_loss.md)."""
 import argparse
 import os
 import sys
@@ -24,6 +28,7 @@ ap.add_argument('--graph', action='store_true', help='op-by-op autograd graph (c
 ap.add_argument('--torch-adam', action='store_true')
 ap.add_argument('--prof', action='store_true')
 ap.add_argument('--thresh', type=float, default=0.05)
+ap.add_argument('--lpips', action='store_true', help='A/B of the use_lpips iteration: cfg.fused_perceptual False against True')
 args = ap.parse_args()
 DEV = 'cuda:0'
 cfg = make_cfg(N_samples=args.samples, smpl_thresh=args.thresh)
@@ -36,9 +41,65 @@ with torch.no_grad():
     for name, p in net.named_parameters():
         if name.endswith('embedder.dense') or name.endswith('embedder.hash'):
             p.normal_(0.0, 0.1, generator=g)
+
+
+def patch(s):
+    bnp, _ = scene.make_scene(512, 512, seed=0, cam_dist=1.8, crop=(256 - s // 2, 256 - s // 2, s, s))
+    return {k: v.to(DEV) for k, v in scene.to_torch(bnp).items()}
+
+
+def lpips_ab():
+    from invr.losses import PerceptualLoss
+    torch.manual_seed(0)
+    net.cfg.use_lpips = True
+    wrap = NetworkWrapper(net, perceptual_loss=PerceptualLoss(allow_random=True))
+    opt = driver.make_optimizer(net, fused=not args.torch_adam)
+    it = 0
+    for side in (64, 56):
+        gb = patch(side)
+        ms = {False: [], True: []}
+        for rep in range(3):                               # interleaved: drift of the box shows as spread within an arm
+            for fused in (False, True):
+                net.cfg.fused_perceptual = fused
+                for _ in range(5):
+                    it += 1
+                    gb['iter_step'] = it + 1
+                    loss = driver.train_step(wrap, opt, gb, it + 1)[0]
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.iters):
+                    it += 1
+                    gb['iter_step'] = it + 1
+                    loss = driver.train_step(wrap, opt, gb, it + 1)[0]
+                torch.cuda.synchronize()
+                ms[fused].append((time.perf_counter() - t0) / args.iters * 1e3)
+        a, b = np.array(ms[False]), np.array(ms[True])
+        print('use_lpips %dx%d patch, %d rays x %d samples: fused_perceptual False %s ms (median %.3f), True %s ms (median %.3f), ratio %.3f, loss %.5f'
+              % (side, side, gb['ray_o'].shape[1], args.samples, np.round(a, 3).tolist(), np.median(a), np.round(b, 3).tolist(), np.median(b),
+                 np.median(b) / np.median(a), float(loss)))
+        from torch.profiler import profile, ProfilerActivity
+        for fused in (False, True):
+            net.cfg.fused_perceptual = fused
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                for _ in range(5):
+                    it += 1
+                    gb['iter_step'] = it + 1
+                    driver.train_step(wrap, opt, gb, it + 1)
+                torch.cuda.synchronize()
+            ev = [e for e in prof.key_averages() if e.device_time_total > 0]
+            print('  fused_perceptual %s: %d device launches per iteration, %.1f us of device time per iteration'
+                  % (fused, sum(e.count for e in ev) // 5, sum(e.device_time_total for e in ev) / 5))
+            if fused:
+                for e in sorted(ev, key=lambda e: -e.device_time_total):
+                    if 'k_perc' in e.key or 'lpips' in e.key:
+                        print('    %-90s x%d per iteration  %.1f us each' % (e.key[:90], e.count // 5, e.device_time_total / e.count))
+
+
+if args.lpips:
+    lpips_ab()
+    sys.exit(0)
 s = args.rays_side
-bnp, _ = scene.make_scene(512, 512, seed=0, cam_dist=1.8, crop=(256 - s // 2, 256 - s // 2, s, s))
-gb = {k: v.to(DEV) for k, v in scene.to_torch(bnp).items()}
+gb = patch(s)
 print('patch rays', gb['ray_o'].shape[1], 'samples', args.samples)
 wrap = NetworkWrapper(net)
 opt = driver.make_optimizer(net, fused=not args.torch_adam)
