@@ -133,7 +133,8 @@ const char* invr_last_error(void);
 #define INVR_ABI_VERSION 2
 int invr_version(void);
 /* sizeof() of the ABI structs as compiled (0 InvrGrid, 1 InvrMlp, 2 InvrPart, 3 InvrModel,
- * 4 InvrScene, 5 InvrWsLayout, 6 InvrMlpBwdOut, 7 InvrAdamTensor): lets a binding verify its struct mirrors. */
+ * 4 InvrScene, 5 InvrWsLayout, 6 InvrMlpBwdOut, 7 InvrAdamTensor, 8 InvrTrainGrads, 9 InvrDeformBwdOut): lets a binding verify its
+ * struct mirrors. */
 size_t invr_sizeof(int32_t which);
 
 /* Bytes of workspace invr_render_fwd needs for n_rays x n_samples with at most max_active
@@ -489,6 +490,35 @@ int invr_part_mlp_bwd_lists(const InvrModel* model, int32_t pid, const int64_t* 
                             const int32_t* l_slot, const InvrMlpBwdOut* out, int32_t latent_full, void* stream);
 int invr_part_wgrad(const float* gz, const float* a, int64_t n_pad, int32_t n_rgb, float* const* dW, float* const* db,
                     const int32_t* count, void* stream);
+
+/* The deformer's backward over a caller-supplied list (stage entry point: the second half of invr_train_bwd's deformer stage, which
+ * builds its list from the pair lists and the pair regulariser's neighbours and then runs exactly this).  Differentiates
+ * resd = 0.05 tanh(MLP(grid(uv(x), frame_dim))) (uv_deformer.py:31-38) at the first *count entries of pts (n_max,3) against the upstream
+ * gradient g_resd (n_max,3): recomputes the forward and writes, per entry, the rows of the matrices below; then ACCUMULATES (atomic float
+ * adds) dW[l] += gz_{l+1}^T a_l, db[l] += column sums of gz_{l+1} (19-32-32-3: dW[0] 32x19, dW[1] 32x32, dW[2] 3x32) and the table
+ * gradients g_dense / g_hash of model->deform_grid (the tables' own layouts; g_dense may be NULL without a separate dense table).
+ * The canonical points carry no gradient.  count is a DEVICE int32; PRECONDITION *count <= n_max (n_max sizes the launches and the
+ * matrices; the host cannot see *count, so it is not checked here).  Nothing at or past *count is read or written.  Uses
+ * scene->tuv / tbounds / frame_dim only.  Runs on `stream` alone. */
+typedef struct InvrDeformBwdOut {
+    float* uvt;       /* (n_max,3)  [u, v, frame_dim] */
+    float* gfeat;     /* (n_max,19) gradient w.r.t. the grid's output [uvt, 16 features] */
+    float* gz1;       /* (n_max,32) gradient w.r.t. layer 1's pre-activation */
+    float* gz2;       /* (n_max,32) */
+    float* gz3;       /* (n_max,4)  column 3 = 0 */
+    float* a0;        /* (n_max,20) layer 1's input (the grid's output), column 19 = 0 */
+    float* a1;        /* (n_max,32) layer 2's input */
+    float* a2;        /* (n_max,32) the head's input */
+} InvrDeformBwdOut;
+int invr_deform_bwd_list(const InvrScene* scene, const InvrModel* model, const float* pts, const float* g_resd, int64_t n_max,
+                         const int32_t* count, const InvrDeformBwdOut* out, float* const* dW, float* const* db, float* g_dense,
+                         float* g_hash, void* stream);
+
+/* Backward of invr_distortion_fwd with respect to the weights (z carries no gradient, inb_renderer.py:96-103):
+ * g_w[r][i] = 2 g_dist[r] sum_j w_j |m_i - m_j|.  weights, z_vals (n_rays,n_samples), g_dist (n_rays) -> g_w (n_rays,n_samples),
+ * every element written. */
+int invr_distortion_bwd(const float* weights, const float* z_vals, const float* g_dist, int64_t n_rays, int32_t n_samples,
+                        float* g_w, void* stream);
 
 /* The training objective of NetworkWrapper.forward (lib/train/trainers/inb_trainer.py:40-98, 176-214 with the plain MSE image term,
  * use_lpips False) on the outputs of invr_train_fwd, one launch each way:

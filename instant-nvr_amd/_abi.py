@@ -33,6 +33,10 @@ class InvrMlpBwdOut(C.Structure):
     _fields_ = [('g_emb', C.c_void_p), ('gz', C.c_void_p), ('a', C.c_void_p), ('n_pad', C.c_int64), ('g_latent', C.c_void_p)]
 
 
+class InvrDeformBwdOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('uvt', 'gfeat', 'gz1', 'gz2', 'gz3', 'a0', 'a1', 'a2')]
+
+
 class InvrAdamTensor(C.Structure):
     _fields_ = [('param', C.c_void_p), ('grad', C.c_void_p), ('exp_avg', C.c_void_p), ('exp_avg_sq', C.c_void_p),
                 ('numel', C.c_int64), ('lr', C.c_float), ('weight_decay', C.c_float), ('bc1', C.c_float), ('bc2_sqrt', C.c_float),
@@ -144,6 +148,8 @@ def _signatures():
         'invr_part_encode_bwd_lists': (C.c_int, [grid, vp, vp, i64, i64, vp, vp, vp, vp]),
         'invr_part_mlp_bwd_lists': (C.c_int, [model, i32, vp, vp, vp, i64, i64, vp, vp, vp, C.POINTER(InvrMlpBwdOut), i32, vp]),
         'invr_part_wgrad': (C.c_int, [vp, vp, i64, i32, C.POINTER(vp), C.POINTER(vp), vp, vp]),
+        'invr_deform_bwd_list': (C.c_int, [scene, model, vp, vp, i64, vp, C.POINTER(InvrDeformBwdOut), C.POINTER(vp), C.POINTER(vp), vp, vp, vp]),
+        'invr_distortion_bwd': (C.c_int, [vp, vp, vp, i64, i32, vp, vp]),
         'invr_train_loss_fwd': (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, i32, vp, vp, vp]),
         'invr_train_loss_bwd': (C.c_int, [vp, vp, vp, i64, f32, f32, f32, i32, vp, vp, vp, vp, vp]),
         'invr_composite_bwd': (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp]),
@@ -194,7 +200,8 @@ def lib():
         if L.invr_version() != ABI_VERSION:
             raise RuntimeError('libinvr.so speaks ABI version %d, this binding %d (include/invr.h INVR_ABI_VERSION): rebuild the library '
                                '(python -m invr.build)' % (L.invr_version(), ABI_VERSION))
-        for i, t in enumerate((InvrGrid, InvrMlp, InvrPart, InvrModel, InvrScene, InvrWsLayout, InvrMlpBwdOut, InvrAdamTensor, InvrTrainGrads)):
+        for i, t in enumerate((InvrGrid, InvrMlp, InvrPart, InvrModel, InvrScene, InvrWsLayout, InvrMlpBwdOut, InvrAdamTensor, InvrTrainGrads,
+                               InvrDeformBwdOut)):
             if L.invr_sizeof(i) != C.sizeof(t):
                 raise RuntimeError('libinvr ABI mismatch: struct %s is %d bytes in the library, %d in the binding'
                                    % (t.__name__, L.invr_sizeof(i), C.sizeof(t)))

@@ -33,6 +33,7 @@ extern "C" size_t invr_sizeof(int32_t which) {
         case 6: return sizeof(InvrMlpBwdOut);
         case 7: return sizeof(InvrAdamTensor);
         case 8: return sizeof(InvrTrainGrads);
+        case 9: return sizeof(InvrDeformBwdOut);
         default: return 0;
     }
 }
@@ -704,6 +705,13 @@ extern "C" int invr_distortion_fwd(const float* weights, const float* z_vals, in
     return launch_distortion(weights, z_vals, n_rays, n_samples, out, (hipStream_t)stream);
 }
 
+extern "C" int invr_distortion_bwd(const float* weights, const float* z_vals, const float* g_dist, int64_t n_rays, int32_t n_samples,
+                                   float* g_w, void* stream) {
+    INVR_CHECK(n_rays == 0 || (weights && z_vals && g_dist && g_w), "invr_distortion_bwd: null pointer");
+    INVR_CHECK(n_samples >= 1, "invr_distortion_bwd: n_samples must be >= 1");
+    return launch_distortion_bwd(weights, z_vals, g_dist, n_rays, n_samples, g_w, (hipStream_t)stream);
+}
+
 extern "C" int invr_composite_fwd(const float* raw, int64_t n_rays, int32_t n_samples, float* weights,
                                   float* rgb_map, float* acc_map, void* stream) {
     INVR_CHECK(n_rays == 0 || (raw && rgb_map && acc_map), "invr_composite_fwd: null pointer");
@@ -1034,6 +1042,23 @@ extern "C" int invr_train_bwd(const InvrScene* scene, const InvrModel* model, in
     if (launch_deform_bwd(a, w, t, make_grid_dev(&model->deform_grid), make_mlp_dev(&model->deform_mlp), g_offset_sum, g_pair_sum, DG, st,
                           ds->s[INVR_NUM_PARTS - 1], ds->dfork, ds->djoin)) return 1;
     return join_wgrads();
+}
+
+extern "C" int invr_deform_bwd_list(const InvrScene* scene, const InvrModel* model, const float* pts, const float* g_resd, int64_t n_max,
+                                    const int32_t* count, const InvrDeformBwdOut* out, float* const* dW, float* const* db, float* g_dense,
+                                    float* g_hash, void* stream) {
+    INVR_CHECK(scene && model && out && dW && db && count, "invr_deform_bwd_list: null scene / model / out / dW / db / count");
+    INVR_CHECK(n_max >= 0 && n_max < (1ll << 31) / 32, "invr_deform_bwd_list: n_max out of range");
+    if (check_deformer_slices(model)) return 1;
+    if (n_max == 0) return 0;
+    INVR_CHECK(pts && g_resd && out->uvt && out->gfeat && out->gz1 && out->gz2 && out->gz3 && out->a0 && out->a1 && out->a2,
+               "invr_deform_bwd_list: null pointer");
+    INVR_CHECK(g_hash && (!model->deform_grid.separate_dense || g_dense) && dW[0] && dW[1] && dW[2] && db[0] && db[1] && db[2],
+               "invr_deform_bwd_list: null gradient pointer");
+    const DeformList d{pts, g_resd, out->uvt, out->gfeat, out->gz1, out->gz2, out->gz3, out->a0, out->a1, out->a2};
+    const DeformGrads G{{dW[0], dW[1], dW[2]}, {db[0], db[1], db[2]}, g_dense, g_hash};
+    return launch_deform_list_bwd(make_scene_dev(scene), make_grid_dev(&model->deform_grid), make_mlp_dev(&model->deform_mlp), d, n_max, count,
+                                  G, (hipStream_t)stream);
 }
 
 __global__ void k_expand_row_grad(const float* __restrict__ rg, int64_t rows, int F, float* __restrict__ out) {

@@ -493,9 +493,9 @@ __device__ __forceinline__ void store_row4(float* dst, const float* v, int n4) {
 #pragma unroll
     for (int k = 0; k < n4; ++k) reinterpret_cast<float4*>(dst)[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
 }
-__global__ __launch_bounds__(DB_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_deform_bwd(SceneDev s, GridDev dg, MlpDev dm, Workspace w, TrainWs t) {
+__global__ __launch_bounds__(DB_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_deform_bwd(SceneDev s, GridDev dg, MlpDev dm, DeformList t, const int32_t* __restrict__ count) {
     __shared__ __attribute__((aligned(16))) float lw[DB_LDS];
-    const int n = w.counters[CNT_DTOT];
+    const int n = *count;
     if ((int64_t)blockIdx.x * DB_BLOCK >= n) return;
     for (int k = threadIdx.x; k < 32 * 19; k += DB_BLOCK) lw[DB_O_W0 + k] = dm.w[0][k];
     for (int k = threadIdx.x; k < 32 * 20; k += DB_BLOCK) lw[DB_O_W0P + k] = (k % 20) < 19 ? dm.w[0][(k / 20) * 19 + k % 20] : 0.0f;
@@ -506,23 +506,23 @@ __global__ __launch_bounds__(DB_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
     __syncthreads();
     const float* W0 = lw + DB_O_W0; const float* W1 = lw + DB_O_W1; const float* W2 = lw + DB_O_W2;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
-        float xb[3] = {t.d_pts[(int64_t)e * 3], t.d_pts[(int64_t)e * 3 + 1], t.d_pts[(int64_t)e * 3 + 2]}, uvt[3];
+        float xb[3] = {t.pts[(int64_t)e * 3], t.pts[(int64_t)e * 3 + 1], t.pts[(int64_t)e * 3 + 2]}, uvt[3];
         DeformActT<true> a;
         deform_fwd_act_w<true>(s, dg, W0, lw + DB_O_B0, W1, lw + DB_O_B1, W2, lw + DB_O_B2, xb, uvt, a);
         float gz3[4];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) gz3[c] = t.d_g[(int64_t)e * 3 + c] * 0.05f * (1.0f - a.th[c] * a.th[c]);
+        for (int c = 0; c < 3; ++c) gz3[c] = t.g[(int64_t)e * 3 + c] * 0.05f * (1.0f - a.th[c] * a.th[c]);
         gz3[3] = 0.0f;
-        store_row4(t.d_gz3 + (int64_t)e * 4, gz3, 1);
+        store_row4(t.gz3 + (int64_t)e * 4, gz3, 1);
         float gz2[32];
 #pragma unroll
         for (int j = 0; j < 32; ++j) {
             const float gh = W2[j] * gz3[0] + W2[32 + j] * gz3[1] + W2[64 + j] * gz3[2];
             gz2[j] = gh * a.s2[j];                                               // softplus'(z) = sigmoid(z)
         }
-        store_row4(t.d_gz2 + (int64_t)e * 32, gz2, 8);
-        store_row4(t.d_a2 + (int64_t)e * 32, a.h2, 8);
-        store_row4(t.d_a1 + (int64_t)e * 32, a.h1, 8);
+        store_row4(t.gz2 + (int64_t)e * 32, gz2, 8);
+        store_row4(t.a2 + (int64_t)e * 32, a.h2, 8);
+        store_row4(t.a1 + (int64_t)e * 32, a.h1, 8);
         // W^T products four outputs at a time: one 16-byte LDS read W[j][4 ib .. 4 ib + 3] feeds four accumulators (every accumulator
         // still sums over j ascending: the element-by-element form's bits)
         float gz1[32];
@@ -539,12 +539,12 @@ __global__ __launch_bounds__(DB_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
             for (int q = 0; q < 4; ++q) gz1[4 * ib + q] = gh[q] * a.s1[4 * ib + q];
             __builtin_amdgcn_sched_barrier(0);
         }
-        store_row4(t.d_gz1 + (int64_t)e * 32, gz1, 8);
+        store_row4(t.gz1 + (int64_t)e * 32, gz1, 8);
         float a0[20];
 #pragma unroll
         for (int i = 0; i < 19; ++i) a0[i] = a.feat[i];
         a0[19] = 0.0f;
-        store_row4(t.d_a0 + (int64_t)e * 20, a0, 5);
+        store_row4(t.a0 + (int64_t)e * 20, a0, 5);
 #pragma unroll
         for (int ib = 0; ib < 5; ++ib) {
             float gf[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -556,11 +556,11 @@ __global__ __launch_bounds__(DB_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                if (4 * ib + q < 19) t.d_gfeat[(int64_t)e * 19 + 4 * ib + q] = gf[q];
+                if (4 * ib + q < 19) t.gfeat[(int64_t)e * 19 + 4 * ib + q] = gf[q];
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
-        for (int c = 0; c < 3; ++c) t.d_uvt[(int64_t)e * 3 + c] = uvt[c];
+        for (int c = 0; c < 3; ++c) t.uvt[(int64_t)e * 3 + c] = uvt[c];
     }
 }
 
@@ -573,15 +573,22 @@ int launch_deform_bwd(const RenderArgs& a, const Workspace& w, const TrainWs& t,
     INVR_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_pair_term_bwd, dim3(256), dim3(256), 0, st, w, t, g_pair_sum);
     INVR_LAUNCH_CHECK();
-    int64_t et = cdiv(t.DM, DB_BLOCK);
-    hipLaunchKernelGGL(k_deform_bwd, dim3((unsigned)(et < 2048 ? (et > 0 ? et : 1) : 2048)), dim3(DB_BLOCK), 0, st, a.scene, dg, dm, w, t);
+    // "differentiate the list": the one copy of the launch code that invr_deform_bwd_list runs too
+    const DeformList d{t.d_pts, t.d_g, t.d_uvt, t.d_gfeat, t.d_gz1, t.d_gz2, t.d_gz3, t.d_a0, t.d_a1, t.d_a2};
+    return launch_deform_list_bwd(a.scene, dg, dm, d, t.DM, w.counters + CNT_DTOT, G, st, side, ev_fork, ev_join);
+}
+
+int launch_deform_list_bwd(const SceneDev& s, const GridDev& dg, const MlpDev& dm, const DeformList& d, int64_t n_max, const int32_t* count,
+                           const DeformGrads& G, hipStream_t st, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
+    int64_t et = cdiv(n_max, DB_BLOCK);
+    hipLaunchKernelGGL(k_deform_bwd, dim3((unsigned)(et < 2048 ? (et > 0 ? et : 1) : 2048)), dim3(DB_BLOCK), 0, st, s, dg, dm, d, count);
     INVR_LAUNCH_CHECK();
     WgradJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
     jobs.n = 3;
-    jobs.j[0] = WgradJob{t.d_gz1, t.d_a0, G.w[0], G.b[0], 0, 32, 20, 32, 19, 19};
-    jobs.j[1] = WgradJob{t.d_gz2, t.d_a1, G.w[1], G.b[1], 0, 32, 32, 32, 32, 32};
-    jobs.j[2] = WgradJob{t.d_gz3, t.d_a2, G.w[2], G.b[2], 0, 4, 32, 3, 32, 32};
+    jobs.j[0] = WgradJob{d.gz1, d.a0, G.w[0], G.b[0], 0, 32, 20, 32, 19, 19};
+    jobs.j[1] = WgradJob{d.gz2, d.a1, G.w[1], G.b[1], 0, 32, 32, 32, 32, 32};
+    jobs.j[2] = WgradJob{d.gz3, d.a2, G.w[2], G.b[2], 0, 4, 32, 3, 32, 32};
     // the weight gradients and the grid^T below both read what k_deform_bwd wrote and nothing of each other: with a side stream
     // (round 6) they run side by side — two latency-bound launches of ~100 us each
     const bool fork = side && ev_fork && ev_join;
@@ -589,11 +596,11 @@ int launch_deform_bwd(const RenderArgs& a, const Workspace& w, const TrainWs& t,
         INVR_HIP(hipEventRecord(ev_fork, st));
         INVR_HIP(hipStreamWaitEvent(side, ev_fork, 0));
     }
-    if (launch_wgrad(jobs, w.counters + CNT_DTOT, t.DM, fork ? side : st)) return 1;
+    if (launch_wgrad(jobs, count, n_max, fork ? side : st)) return 1;
     if (fork) INVR_HIP(hipEventRecord(ev_join, side));
     // grid^T: table gradients of the deformer's 8 x 2 grid (the (u,v,t) input carries no gradient)
-    int rc = launch_deform_slice_bwd(dg, a.scene.frame_dim, t.d_uvt, t.d_gfeat, t.DM, w.counters + CNT_DTOT, G.dense, G.hash, st);
-    if (rc < 0) rc = launch_grid_encode_bwd_generic(dg, t.d_uvt, t.d_gfeat, t.DM, G.dense, G.hash, nullptr, st, w.counters + CNT_DTOT);
+    int rc = launch_deform_slice_bwd(dg, s.frame_dim, d.uvt, d.gfeat, n_max, count, G.dense, G.hash, st);
+    if (rc < 0) rc = launch_grid_encode_bwd_generic(dg, d.uvt, d.gfeat, n_max, G.dense, G.hash, nullptr, st, count);
     if (fork) INVR_HIP(hipStreamWaitEvent(st, ev_join, 0));
     return rc;
 }

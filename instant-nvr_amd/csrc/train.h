@@ -24,6 +24,11 @@ struct TrainWs {
 };
 
 struct DeformGrads { float* w[3]; float* b[3]; float* dense; float* hash; };
+// the list the deformer is differentiated over: point + upstream gradient in, the per-entry matrices of k_deform_bwd out (shapes as in TrainWs)
+struct DeformList {
+    const float* pts; const float* g;
+    float* uvt; float* gfeat; float* gz1; float* gz2; float* gz3; float* a0; float* a1; float* a2;
+};
 
 int launch_train_terms(const RenderArgs& a, const Workspace& w, const TrainWs& t, const GridDev& dg, const MlpDev& dm,
                        const float* noise, hipStream_t st);
@@ -31,6 +36,10 @@ int launch_distortion_bwd(const float* weights, const float* z, const float* g_d
 int launch_merge_bwd(const Workspace& w, int aggr, const float4* g_rawfull, float4* g_raws, hipStream_t st);
 int launch_deform_bwd(const RenderArgs& a, const Workspace& w, const TrainWs& t, const GridDev& dg, const MlpDev& dm,
                       const float* g_off_sum, const float* g_pair_sum, const DeformGrads& G, hipStream_t st, hipStream_t side = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr);
+// the second half of launch_deform_bwd: k_deform_bwd -> the three weight-gradient jobs -> grid^T over the first *count (DEVICE) <= n_max
+// entries of a list; the gradients are accumulated into.  side / ev_fork / ev_join: the optional side stream of the weight gradients
+int launch_deform_list_bwd(const SceneDev& s, const GridDev& dg, const MlpDev& dm, const DeformList& d, int64_t n_max, const int32_t* count,
+                           const DeformGrads& G, hipStream_t st, hipStream_t side = nullptr, hipEvent_t ev_fork = nullptr, hipEvent_t ev_join = nullptr);
 struct WgradJob;
 struct WgradJobs;
 int launch_part_wgrad(const float* gz, const float* a, int64_t lcap, int n_rgb, float* const* dW, float* const* db,

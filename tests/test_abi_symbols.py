@@ -60,7 +60,7 @@ def test_library_exports_header_symbols():
     assert int(re.search(r'#define INVR_ABI_VERSION (\d+)', hdr).group(1)) == _abi.ABI_VERSION
     # every declaration parses as a prototype, and the binding's one table states each with the header's types, in the header's order
     protos = header_prototypes()
-    assert len(protos) == 50
+    assert len(protos) == 52
     assert sorted(name for _, name, _ in protos) == names, 'an invr_ declaration of the header did not parse as a prototype'
     assert [name for _, name, _ in protos] == list(_abi.SIGNATURES) == _abi.EXPORTS
     for ret, name, params in protos:
@@ -146,7 +146,7 @@ def test_struct_sizes_match_header():
     assert C.sizeof(_abi.InvrAdamTensor) == 4 * 8 + 8 + 4 * 4 + 8 + 2 * 4
     assert C.sizeof(_abi.InvrTrainGrads) == 5 * (8 + 4 * 4 * 8 + 8) + 2 * 8 + 2 * 4 * 8 + 8
     for i, t in enumerate((_abi.InvrGrid, _abi.InvrMlp, _abi.InvrPart, _abi.InvrModel, _abi.InvrScene, _abi.InvrWsLayout, _abi.InvrMlpBwdOut,
-                           _abi.InvrAdamTensor, _abi.InvrTrainGrads)):
+                           _abi.InvrAdamTensor, _abi.InvrTrainGrads, _abi.InvrDeformBwdOut)):
         assert L.invr_sizeof(i) == C.sizeof(t), t
 
 

@@ -1,4 +1,4 @@
-"""GPU: two training-side entry points that had no stage test of their own, against float64.
+"""GPU: three training-side entry points that had no stage test of their own, against float64.
 
 invr_distortion_fwd vs the oracle's distortion_loss in float64 at ragged shapes (S below / at / above one wave, one ray per
 workgroup tail), weights ~60 % exact zeros, jittered ascending z:
@@ -6,6 +6,9 @@ workgroup tail), weights ~60 % exact zeros, jittered ascending z:
 noise = the larger of the fp32 oracle's deviation and the largest move of the float64 value under 4 ulp-sized perturbations of z
 (tests/conditioning.py's convention: |m_i - m_j| of neighbouring samples cancels).  All summands are non-negative, so the value is its
 own absolute sum; 2 S bounds the depth of a sum taken row by row and then over the rows (S + S/64 + 6 additions, 5 roundings per term).
+
+invr_distortion_bwd vs float64 autograd of the same function with respect to the weights, on the same inputs: the same form of bound
+with A = 2 |g| sum_j |w_j| |m_i - m_j| (test_distortion_bwd_vs_float64).
 
 invr_train_loss_fwd / _bwd vs the closed form of include/invr.h in float64.  The forward sums in double, so what is left are the
 fp32 roundings of a term (d = rgb - gt, d * d: (1 + e)^3), the final casts and one division each:
@@ -62,6 +65,58 @@ def test_distortion_fwd_vs_float64(R, S):
     assert not torch.isnan(out).any()
     assert (err <= allow).all(), float((err - allow).max())
     assert (out[exact == 0] == 0).all()
+
+
+def _distortion_inputs(R, S):
+    """The inputs of test_distortion_fwd_vs_float64 (same seed, same draws in the same order) -> (w, z, generator)."""
+    g = torch.Generator().manual_seed(100 * R + S)
+    w = torch.rand(R, S, generator=g) * (torch.rand(R, S, generator=g) > 0.6) * (2.0 / S)
+    if R > 2:
+        w[1] = 0.0
+    z = 2.0 + 2.0 * (torch.arange(S)[None] + torch.rand(R, S, generator=g) * 0.9) / S
+    return w, z, g
+
+
+@pytest.mark.parametrize('R,S', [(1, 1), (7, 5), (33, 64), (20, 65), (9, 128), (5, 200), (4097, 64)])
+def test_distortion_bwd_vs_float64(R, S):
+    """invr_distortion_bwd vs float64 autograd of the oracle's distortion_loss with respect to the weights, on the forward test's
+    inputs and a seeded non-zero g_dist, every element:
+        |kernel - exact| <= 8 noise + 2 S 2^-24 A,        A = 2 |g| sum_j |w_j| |m_i - m_j|
+    noise as in the forward test (the fp32 autograd's deviation; 4 ulp-sized perturbations of z).  The rows of an all-zero ray are
+    exactly 0."""
+    w, z, g = _distortion_inputs(R, S)
+    gd = torch.randn(R, generator=g)
+    gd = torch.where(gd.abs() < 0.05, torch.full_like(gd, 0.5), gd)           # non-zero
+    out = torch.full((R, S), float('nan'), device=DEV)
+    wd, zd, gdd = w.to(DEV).contiguous(), z.to(DEV).contiguous(), gd.to(DEV).contiguous()
+    _abi.check(_abi.lib().invr_distortion_bwd(_abi.ptr(wd), _abi.ptr(zd), _abi.ptr(gdd), R, S, _abi.ptr(out), _abi.stream_ptr()))
+    sync()
+    out = out.cpu()
+
+    def grad(wt, zt, dtype):
+        wt = wt.to(dtype).clone().requires_grad_()
+        O.distortion_loss(wt, zt.to(dtype)).backward(gd.to(dtype))
+        return wt.grad
+    exact = grad(w, z, torch.float64)
+    o32 = grad(w, z, torch.float32)
+    noise = (o32.double() - exact).abs()
+    for _ in range(4):
+        s = torch.randint(0, 2, z.shape, generator=g).double() * 2.0 - 1.0
+        noise = torch.maximum(noise, (grad(w, z.double() * (1.0 + s * 2.0 ** -23), torch.float64) - exact).abs())
+    nz = torch.cat([z[:, 1:], z[:, -1:]], -1).double()
+    mid = (z.double() + nz) / 2
+    A = 2.0 * gd.double().abs()[:, None] * (w.double().abs()[:, None, :] * (mid[:, :, None] - mid[:, None, :]).abs()).sum(-1)
+    assert (A >= exact.abs() * (1 - 1e-12)).all()
+    allow = 8.0 * noise + 2.0 * S * U * A
+    err = (out.double() - exact).abs()
+    den = noise + 2.0 * U * A
+    print('DISTB R %d S %d  K_kernel %.3g K_oracle32 %.3g' % (R, S, float((err / den.clamp(min=1e-300)).max()),
+                                                              float(((o32.double() - exact).abs() / den.clamp(min=1e-300)).max())))
+    assert not torch.isnan(out).any()
+    assert (err <= allow).all(), float((err - allow).max())
+    assert (out[A == 0] == 0).all()
+    if R > 2:
+        assert not w[1].any() and (out[1] == 0).all()                           # the ray that hit nothing
 
 
 def _f32(v):
