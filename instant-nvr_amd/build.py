@@ -8,8 +8,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'libinvr.so')
 SOURCES = ['invr_abi.hip', 'k_cull.hip', 'k_knn.hip', 'k_warp.hip', 'k_encode.hip', 'k_mlp.hip', 'k_composite.hip', 'k_rays.hip', 'k_prep.hip', 'k_optim.hip', 'k_mlp_bwd.hip', 'k_train.hip', 'k_metrics.hip', 'k_perceptual.hip']
-HEADERS = ['common.h', 'pipeline.h', 'grid_generic.h', 'mlp_common.h', 'train.h', os.path.join('..', '..', 'include', 'invr.h'),
-           os.path.join('..', '..', 'include', 'invr_perceptual.h')]
+INCLUDE = os.path.join(HERE, '..', 'include')
+
+
+def headers():
+    """Every header a source may include: an edit to any of them rebuilds every object."""
+    return ([os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith('.h')]
+            + [os.path.join(INCLUDE, h) for h in ('invr.h', 'invr_perceptual.h')])
+
+
 # -ffp-contract=off: FMAs only where the source says fmaf(), so the discrete decisions of the path
 # (cull / flag thresholds, integer cell selection) see the same fp32 arithmetic as the reference.
 # -fno-slp-vectorize (round 6): no COMPILER-generated packed-fp32 math (v_pk_mul / v_pk_add / v_pk_fma_f32 with op_sel shuffles).  The SLP
@@ -38,7 +45,7 @@ def build(force=False, verbose=True):
     cc = hipcc()
     objdir = os.path.join(HERE, 'build')
     os.makedirs(objdir, exist_ok=True)
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS]
+    hdrs = headers()
     stamp = os.path.join(objdir, 'flags.txt')              # (objects built with other flags are stale too)
     if not os.path.exists(stamp) or open(stamp).read() != ' '.join(FLAGS):
         force = True

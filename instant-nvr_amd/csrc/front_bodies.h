@@ -401,7 +401,7 @@ __device__ __forceinline__ void vertex_mats_body(const SceneDev& s, const KnnInd
     }
 }
 
-// ---- per-frame t-slices of the deformer grid (k_warp.hip: k_deform_pairs_slice) ---------------------------
+// ---- per-frame t-slices of the deformer grid (k_warp.hip: k_deform_pairs) ---------------------------
 struct DfSliceInfo { int off[INVR_MAX_LEVELS + 1]; };
 
 __device__ __forceinline__ void deform_slice_body(const GridDev& dg, const DfSliceInfo& si, const float* __restrict__ frame_dim,

@@ -14,7 +14,7 @@
 #include <string.h>
 #include "pipeline.h"
 #include "grid_generic.h"
-#include "mlp_common.h"
+#include "deform_mlp.h"
 #include "train.h"
 
 #define TR_BLOCK 256
@@ -81,80 +81,20 @@ __global__ __launch_bounds__(TR_BLOCK) void k_train_terms(Workspace w, TrainWs t
     if (blockIdx.x == 0 && threadIdx.x == 0) t.terms[TERM_OFFSET_ROWS] = (float)rows;
 }
 
-// ---- thread-per-point deformer (uv_deformer.py:31-38), forward with kept activations --------------------------------
-// (BWD: the backward's recompute — activations AND their derivative factors softplus'(z) = sigmoid(z) formed from the pre-activation
-// (sigmoid_acc: ~3 ulp RELATIVE for every z).  The earlier form 1 - exp(-softplus(z)) is a cancellation for z < 0: 6e-8 ABSOLUTE error on a
-// factor ~e^z, and with Adam's eps = 1e-15 every extra bit of gradient noise flips the sign of more rounding-level steps — the
-// deformer's first layer agreed with the float32 oracle on 0.67-0.94 of its elements after three steps, 0.99 now
-// (tests/test_gpu_training.py::test_configs3_real_shape_three_steps_vs_oracle_autograd))
-template <bool BWD> struct DeformActT { float feat[19]; float h1[32]; float h2[32]; float th[3]; float s1[BWD ? 32 : 1]; float s2[BWD ? 32 : 1]; };
-typedef DeformActT<false> DeformAct;
-
-// (the weights through any pointers: the MlpDev's global tensors, or a workgroup's LDS copy — same operations, same order)
-template <bool BWD>
-__device__ __forceinline__ void deform_fwd_act_w(const SceneDev& s, const GridDev& dg, const float* W0, const float* B0, const float* W1,
-                                                 const float* B1, const float* W2, const float* B2, const float* xb, float* uvt,
-                                                 DeformActT<BWD>& a) {
-    sample_volume_dev<2>(s.tuv, 0, xb[0], xb[1], xb[2], uvt);
-    uvt[2] = s.frame_dim[0];
-    grid_encode_concat<8, 2>(dg, uvt, a.feat);
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        float acc = B0[j];
-#pragma unroll
-        for (int i = 0; i < 19; ++i) acc = fmaf(W0[j * 19 + i], a.feat[i], acc);
-        a.h1[j] = softplus_f(acc);
-        if (BWD) a.s1[j] = sigmoid_acc(acc);
-        if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);       // (keeps the weight loads of later neurons from being hoisted: registers)
-    }
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        float acc = B1[j];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) acc = fmaf(W1[j * 32 + i], a.h1[i], acc);
-        a.h2[j] = softplus_f(acc);
-        if (BWD) a.s2[j] = sigmoid_acc(acc);
-        if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        float acc = B2[j];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) acc = fmaf(W2[j * 32 + i], a.h2[i], acc);
-        a.th[j] = tanhf(acc);
-    }
-}
-template <bool BWD>
-__device__ __forceinline__ void deform_fwd_act(const SceneDev& s, const GridDev& dg, const MlpDev& dm, const float* xb, float* uvt,
-                                               DeformActT<BWD>& a) {
-    deform_fwd_act_w<BWD>(s, dg, dm.w[0], dm.b[0], dm.w[1], dm.b[1], dm.w[2], dm.b[2], xb, uvt, a);
-}
-
 // neighbours of the selected rows through the deformer; pair term of crit.reg_raw_crit (crit.py:8-18):
 // || v_nb / (|v_nb| + 1e-8) - v_self / (|v_self| + 1e-8) ||, summed (the mean's divisor n stays on the device)
 // (round 6: the MLP's weights from an LDS copy, as k_deform_bwd — they were ~1100 wave-uniform vector loads per thread)
-#define PT_O_B0 (32 * 19)
-#define PT_O_W1 (PT_O_B0 + 32)
-#define PT_O_B1 (PT_O_W1 + 32 * 32)
-#define PT_O_W2 (PT_O_B1 + 32)
-#define PT_O_B2 (PT_O_W2 + 3 * 32)
 __global__ __launch_bounds__(128) void k_pair_term_fwd(SceneDev s, GridDev dg, MlpDev dm, Workspace w, TrainWs t) {
     __shared__ float red[TR_BLOCK / 64];
-    __shared__ __attribute__((aligned(16))) float lw[PT_O_B2 + 4];
+    __shared__ __attribute__((aligned(16))) float lw[DM_LDS];
     const int nsel = min(w.counters[CNT_NB], (int)t.NB);
     float acc = 0.0f;
-    if ((int)(blockIdx.x * blockDim.x) < nsel) {            // (block-uniform: workgroups without a row stage nothing)
-        for (int k = threadIdx.x; k < 32 * 19; k += blockDim.x) lw[k] = dm.w[0][k];
-        for (int k = threadIdx.x; k < 32 * 32; k += blockDim.x) lw[PT_O_W1 + k] = dm.w[1][k];
-        if (threadIdx.x < 96) lw[PT_O_W2 + threadIdx.x] = dm.w[2][threadIdx.x];
-        if (threadIdx.x < 32) { lw[PT_O_B0 + threadIdx.x] = dm.b[0][threadIdx.x]; lw[PT_O_B1 + threadIdx.x] = dm.b[1][threadIdx.x]; }
-        if (threadIdx.x < 3) lw[PT_O_B2 + threadIdx.x] = dm.b[2][threadIdx.x];
-    }
+    if ((int)(blockIdx.x * blockDim.x) < nsel) stage_deform_weights(lw, dm, blockDim.x);      // (block-uniform: workgroups without a row stage nothing)
     __syncthreads();
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nsel; k += gridDim.x * blockDim.x) {
         float xb[3] = {t.nb_x[(int64_t)k * 3], t.nb_x[(int64_t)k * 3 + 1], t.nb_x[(int64_t)k * 3 + 2]}, uvt[3];
         DeformAct a;
-        deform_fwd_act_w<false>(s, dg, lw, lw + PT_O_B0, lw + PT_O_W1, lw + PT_O_B1, lw + PT_O_W2, lw + PT_O_B2, xb, uvt, a);
+        deform_fwd_act_w<false>(s, dg, lw, lw + DM_O_B0, lw + DM_O_W1, lw + DM_O_B1, lw + DM_O_W2, lw + DM_O_B2, xb, uvt, a);
         float vn[3], vs[3];
         const int ref = t.nb_ref[k], p = ref >> 28, i = ref & 0x0FFFFFFF;
 #pragma unroll
@@ -481,13 +421,7 @@ __global__ __launch_bounds__(256) void k_pair_term_bwd(Workspace w, TrainWs t, c
 // traffic per 16 bytes of weights), 256 registers per thread instead of 128 + 151 spilled dwords, the row-major (gz, a) rows stored
 // as float4 (a lane's row is contiguous: 8 stores instead of 32 per 32-wide row).  Same operations in the same order: same bits.
 #define DB_BLOCK 256
-#define DB_O_W0 0                       // 32 x 19
-#define DB_O_B0 (DB_O_W0 + 32 * 19)
-#define DB_O_W1 (DB_O_B0 + 32)          // 32 x 32
-#define DB_O_B1 (DB_O_W1 + 32 * 32)
-#define DB_O_W2 (DB_O_B1 + 32)          // 3 x 32
-#define DB_O_B2 (DB_O_W2 + 3 * 32)
-#define DB_O_W0P (DB_O_B2 + 4)          // 32 x 20: W0 with rows padded to 20 (16-byte aligned rows for the W0^T product)
+#define DB_O_W0P DM_LDS                  // behind the shared image — 32 x 20: W0 with rows padded to 20 (16-byte aligned rows for the W0^T product)
 #define DB_LDS (DB_O_W0P + 32 * 20)
 __device__ __forceinline__ void store_row4(float* dst, const float* v, int n4) {
 #pragma unroll
@@ -497,18 +431,14 @@ __global__ __launch_bounds__(DB_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))
     __shared__ __attribute__((aligned(16))) float lw[DB_LDS];
     const int n = *count;
     if ((int64_t)blockIdx.x * DB_BLOCK >= n) return;
-    for (int k = threadIdx.x; k < 32 * 19; k += DB_BLOCK) lw[DB_O_W0 + k] = dm.w[0][k];
+    stage_deform_weights(lw, dm, DB_BLOCK);
     for (int k = threadIdx.x; k < 32 * 20; k += DB_BLOCK) lw[DB_O_W0P + k] = (k % 20) < 19 ? dm.w[0][(k / 20) * 19 + k % 20] : 0.0f;
-    for (int k = threadIdx.x; k < 32 * 32; k += DB_BLOCK) lw[DB_O_W1 + k] = dm.w[1][k];
-    if (threadIdx.x < 96) lw[DB_O_W2 + threadIdx.x] = dm.w[2][threadIdx.x];
-    if (threadIdx.x < 32) { lw[DB_O_B0 + threadIdx.x] = dm.b[0][threadIdx.x]; lw[DB_O_B1 + threadIdx.x] = dm.b[1][threadIdx.x]; }
-    if (threadIdx.x < 3) lw[DB_O_B2 + threadIdx.x] = dm.b[2][threadIdx.x];
     __syncthreads();
-    const float* W0 = lw + DB_O_W0; const float* W1 = lw + DB_O_W1; const float* W2 = lw + DB_O_W2;
+    const float* W1 = lw + DM_O_W1; const float* W2 = lw + DM_O_W2;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += gridDim.x * blockDim.x) {
         float xb[3] = {t.pts[(int64_t)e * 3], t.pts[(int64_t)e * 3 + 1], t.pts[(int64_t)e * 3 + 2]}, uvt[3];
         DeformActT<true> a;
-        deform_fwd_act_w<true>(s, dg, W0, lw + DB_O_B0, W1, lw + DB_O_B1, W2, lw + DB_O_B2, xb, uvt, a);
+        deform_fwd_act_w<true>(s, dg, lw + DM_O_W0, lw + DM_O_B0, W1, lw + DM_O_B1, W2, lw + DM_O_B2, xb, uvt, a);
         float gz3[4];
 #pragma unroll
         for (int c = 0; c < 3; ++c) gz3[c] = t.g[(int64_t)e * 3 + c] * 0.05f * (1.0f - a.th[c] * a.th[c]);

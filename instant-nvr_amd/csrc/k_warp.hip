@@ -10,8 +10,8 @@
 // One thread per pair.  The 24 joint matrices and the deformer MLP weights are wave-uniform:
 // they are read through the scalar path (s_load) and used as SGPR operands of v_fmac.
 // The deformer tables are 0.34 MB (L2 resident).
-#include "pipeline.h"
-#include "grid_generic.h"
+#include <type_traits>
+#include "deform_mlp.h"
 #include "front_bodies.h"
 
 #define WARP_BLOCK 128
@@ -59,48 +59,10 @@ __device__ __forceinline__ void warp_with_mats(const Mat34& Aw, const Mat34& Bw,
     }
 }
 
-// Deformer.forward for one canonical point (uv_deformer.py:31-38)
-__device__ __forceinline__ void deform_point(const SceneDev& s, const GridDev& dg, const float* __restrict__ W0,
-                                             const float* __restrict__ B0, const float* __restrict__ W1,
-                                             const float* __restrict__ B1, const float* __restrict__ W2,
-                                             const float* __restrict__ B2, const float* xb, float* resd) {
-    float uvt[3];
-    sample_volume_dev<2>(s.tuv, 0, xb[0], xb[1], xb[2], uvt);
-    uvt[2] = s.frame_dim[0];
-    float feat[19];
-    grid_encode_concat<8, 2>(dg, uvt, feat);
-    float h1[32], h2[32];
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        float acc = B0[j];
-#pragma unroll
-        for (int i = 0; i < 19; ++i) acc = fmaf(W0[j * 19 + i], feat[i], acc);
-        h1[j] = softplus_f(acc);
-    }
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        float acc = B1[j];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) acc = fmaf(W1[j * 32 + i], h1[i], acc);
-        h2[j] = softplus_f(acc);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        float acc = B2[j];
-#pragma unroll
-        for (int i = 0; i < 32; ++i) acc = fmaf(W2[j * 32 + i], h2[i], acc);
-        resd[j] = 0.05f * tanhf(acc);
-    }
-}
-
 // ---- dense variant (invr_warp_deform): every (point, part) --------------------------------------
-__global__ __launch_bounds__(WARP_BLOCK) void k_warp_dense(SceneDev s, GridDev dg, const float* __restrict__ A,
-                                                           const float* __restrict__ big_A, const float* __restrict__ W0,
-                                                           const float* __restrict__ B0, const float* __restrict__ W1,
-                                                           const float* __restrict__ B1, const float* __restrict__ W2,
-                                                           const float* __restrict__ B2, const float* pose_pts,
-                                                           const float* pose_dirs, const float* bw, const uint8_t* flag,
-                                                           int64_t n, float* tpose, float* tdirs, float* resd) {
+__global__ __launch_bounds__(WARP_BLOCK) void k_warp_dense(SceneDev s, GridDev dg, MlpDev dm, const float* pose_pts, const float* pose_dirs,
+                                                           const float* bw, const uint8_t* flag, int64_t n, float* tpose, float* tdirs,
+                                                           float* resd) {
     int64_t q = (int64_t)blockIdx.x * WARP_BLOCK + threadIdx.x;     // pair index = point*P + part
     if (q >= n * INVR_NUM_PARTS) return;
     int64_t i = q / INVR_NUM_PARTS;
@@ -108,8 +70,14 @@ __global__ __launch_bounds__(WARP_BLOCK) void k_warp_dense(SceneDev s, GridDev d
 #pragma unroll
     for (int j = 0; j < INVR_NUM_JOINTS; ++j) b[j] = bw[q * INVR_NUM_JOINTS + j];
     float xb[3], db[3], r[3] = {0.f, 0.f, 0.f};
-    warp_point(A, big_A, b, pose_pts + i * 3, pose_dirs + i * 3, xb, db);
-    if (flag[q]) deform_point(s, dg, W0, B0, W1, B1, W2, B2, xb, r);
+    warp_point(s.A, s.big_A, b, pose_pts + i * 3, pose_dirs + i * 3, xb, db);
+    if (flag[q]) {
+        float uvt[3];
+        DeformAct a;
+        deform_fwd_act<false>(s, dg, dm, xb, uvt, a);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[c] = 0.05f * a.th[c];
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         tpose[q * 3 + c] = xb[c] + r[c];
@@ -123,8 +91,7 @@ int launch_warp_deform_dense(const SceneDev& s, const GridDev& dg, const MlpDev&
                              float* tpose, float* tdirs, float* resd, hipStream_t st) {
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_warp_dense, dim3((unsigned)cdiv(n * INVR_NUM_PARTS, WARP_BLOCK)), dim3(WARP_BLOCK), 0, st,
-                       s, dg, s.A, s.big_A, dm.w[0], dm.b[0], dm.w[1], dm.b[1], dm.w[2], dm.b[2], pose_pts, pose_dirs, bw, flag, n,
-                       tpose, tdirs, resd);
+                       s, dg, dm, pose_pts, pose_dirs, bw, flag, n, tpose, tdirs, resd);
     INVR_LAUNCH_CHECK();
     return 0;
 }
@@ -186,25 +153,20 @@ __global__ __launch_bounds__(WARP_BLOCK) void k_warp_pairs(RenderArgs a, Workspa
 
 // Residual deformer of the pair lists on the fp32 matrix cores (same D^T = W . X^T orientation as
 // k_part_mlp: 16 pairs = the N columns of v_mfma_f32_16x16x4_f32, accumulators of one layer are the B
-// operands of the next).  A wave handles 64 pairs per iteration:
+// operands of the next; weight image and K order: deform_mlp.h).  A wave handles 64 pairs per iteration:
 //   1. lane j: canonical point of pair j, trilinear (u,v) from the UV volume
 //   2. four 16-pair tiles; in tile cb lane (g = lane>>4, col = lane&15) encodes levels 2g and 2g+1 of
-//      pair cb*16+col (16 float2 gathers per lane, no index math duplicated between lanes) — the K order
-//      of layer 1 is permuted to match: k-slot (s<4, g) = feature 3 + 2*(2g + s/2) + s%2, (4, g) = uvt[g]
+//      pair cb*16+col (no index math duplicated between lanes)
 //   3. 19(20) -> 32 -> 32 on MFMA (10 + 16 instructions per tile), 32 -> 3 head as VALU dots, 0.05*tanh
 //   4. lane j = cb*16+col takes the result of "its" pair back and writes tpose / resd, coalesced.
-typedef float dfx4 __attribute__((ext_vector_type(4)));
-#define DF_BLOCK 256
-#define DF_O_W1 0                       // 5 k-steps * 2 m-tiles * 64 lanes
-#define DF_O_W2 (DF_O_W1 + 5 * 2 * 64)  // 8 * 2 * 64
-#define DF_O_B1 (DF_O_W2 + 8 * 2 * 64)  // 32
-#define DF_O_B2 (DF_O_B1 + 32)          // 32
-#define DF_O_V (DF_O_B2 + 32)           // 3 * 32, slot order [c][g*8 + mt*4 + r]
-#define DF_O_B3 (DF_O_V + 96)           // 3 (+1)
-#define DF_LDS (DF_O_B3 + 4)
-
-__device__ __forceinline__ int df_col(int s, int g) { return s < 4 ? 3 + 2 * (2 * g + (s >> 1)) + (s & 1) : (g < 3 ? g : -1); }
-
+// One body, two level look-ups (SLICE):
+//   true  — per-frame t-slices.  The deformer's third grid coordinate is frame_dim (uv_deformer.py:33-34): ONE value for the whole
+//           call.  So per level the z corner pair and its weight are the same for every point, and the 3-D grid collapses to a 2-D
+//           (u,v) table  S_l[cx][cy] = (1-tz) row(cx,cy,c0z) + tz row(cx,cy,c1z)  (hashed levels included: the slice of a hashed
+//           level is materialised densely).  sum_l res_l^2 = 2959 entries (24 KB) for the reference's 8 levels — built once per call
+//           by deform_slice_body (k_front_scene) and held in LDS behind the weights, so the 64 L1-line gathers per pair that bounded
+//           the kernel become 32 ds_read_b64.  (u,v) index math stays the reference's.
+//   false — grids whose slices exceed DF_SLICE_MAX (deform_slices_fit): 16 float2 gathers per lane and level pair from the 3-D tables.
 struct LaneLevel2 { const float2* tab; int res; float cell; bool hashed; };
 
 // one level of the 8x2 deformer grid for this lane's point: same arithmetic and accumulation order as
@@ -238,148 +200,6 @@ __device__ __forceinline__ void lane_level_f2(const GridDev& dg, const LaneLevel
     }
 }
 
-#define DF_CB 2                         // 16-pair tiles in flight per wave (register budget)
-__global__ __launch_bounds__(DF_BLOCK) void k_deform_pairs(RenderArgs a, Workspace w, GridDev dg,
-                                                           const float* __restrict__ W0, const float* __restrict__ B0,
-                                                           const float* __restrict__ W1, const float* __restrict__ B1,
-                                                           const float* __restrict__ W2, const float* __restrict__ B2) {
-    __shared__ float lds[DF_LDS];
-    const int p = blockIdx.y;
-    const int cnt = w.counters[CNT_PAIRS + p];
-    if ((int64_t)blockIdx.x * DF_BLOCK >= cnt) return;
-    for (int t = threadIdx.x; t < 5 * 2 * 64; t += DF_BLOCK) {
-        const int ln = t & 63, mt = (t >> 6) & 1, s = t >> 7, g = ln >> 4, i = ln & 15, col = df_col(s, g);
-        lds[DF_O_W1 + t] = col >= 0 ? W0[(16 * mt + i) * 19 + col] : 0.0f;
-    }
-    for (int t = threadIdx.x; t < 8 * 2 * 64; t += DF_BLOCK) {
-        const int ln = t & 63, mt = (t >> 6) & 1, s = t >> 7, g = ln >> 4, i = ln & 15;
-        lds[DF_O_W2 + t] = W1[(16 * mt + i) * 32 + 16 * (s >> 2) + 4 * g + (s & 3)];
-    }
-    if (threadIdx.x < 32) {
-        const int t = threadIdx.x, g = t >> 3, u = t & 7, hc = 16 * (u >> 2) + 4 * g + (u & 3);
-        lds[DF_O_B1 + t] = B0[t];
-        lds[DF_O_B2 + t] = B1[t];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) lds[DF_O_V + c * 32 + t] = W2[c * 32 + hc];
-        if (t < 3) lds[DF_O_B3 + t] = B2[t];
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
-    LaneLevel2 LA, LB;                   // levels 2g and 2g+1
-    LA.tab = LB.tab = nullptr; LA.res = LB.res = 2; LA.cell = LB.cell = 1.0f; LA.hashed = LB.hashed = false;
-#pragma unroll
-    for (int l = 0; l < 8; ++l) {
-        LaneLevel2 t;
-        t.hashed = l >= dg.start_hash;
-        t.res = dg.res[l];
-        t.cell = dg.cell[l];
-        const float* tb = dg.separate_dense ? (t.hashed ? dg.hash + (int64_t)(l - dg.start_hash) * dg.T * 2 : dg.dense + dg.dense_off[l] * 2)
-                                            : dg.hash + (int64_t)l * dg.T * 2;
-        t.tab = reinterpret_cast<const float2*>(tb);
-        if (l == 2 * g) LA = t;
-        if (l == 2 * g + 1) LB = t;
-    }
-    const float gb0 = dg.bounds[0], gb1 = dg.bounds[1], gb2 = dg.bounds[2];
-    const float ge0 = dg.bounds[3] - gb0, ge1 = dg.bounds[4] - gb1, ge2 = dg.bounds[5] - gb2;
-    const float tn = (a.scene.frame_dim[0] - gb2) / ge2;                 // uvt[2] = frame_dim, normalised (:112)
-    float* lx = w.l_x[p];
-    float* lr = w.l_r[p];
-
-    for (int64_t base = (int64_t)blockIdx.x * DF_BLOCK + wv * 64; base < cnt; base += (int64_t)gridDim.x * DF_BLOCK) {
-        const int64_t i = min(base + lane, (int64_t)cnt - 1);
-        float xb[3], uv[2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) xb[c] = lx[c * w.lcap + i];
-        sample_volume_dev<2>(a.scene.tuv, 0, xb[0], xb[1], xb[2], uv);
-        const float un = (uv[0] - gb0) / ge0, vn = (uv[1] - gb1) / ge1;
-        float r3[3] = {0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int half = 0; half < 4 / DF_CB; ++half) {
-        float eb[DF_CB][5];
-#pragma unroll
-        for (int cb = 0; cb < DF_CB; ++cb) {
-            const int src = (half * DF_CB + cb) * 16 + col;
-            const float uu = __shfl(un, src), vv = __shfl(vn, src);
-            lane_level_f2(dg, LA, uu, vv, tn, eb[cb][0], eb[cb][1]);
-            lane_level_f2(dg, LB, uu, vv, tn, eb[cb][2], eb[cb][3]);
-            eb[cb][4] = g == 0 ? uu : (g == 1 ? vv : (g == 2 ? tn : 0.0f));
-        }
-        // ---- layer 1: 20 -> 32
-        dfx4 h[DF_CB][2];
-#pragma unroll
-        for (int cb = 0; cb < DF_CB; ++cb)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) h[cb][mt][r] = lds[DF_O_B1 + 16 * mt + 4 * g + r];
-#pragma unroll
-        for (int s = 0; s < 5; ++s)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                const float aw = lds[DF_O_W1 + (s * 2 + mt) * 64 + lane];
-#pragma unroll
-                for (int cb = 0; cb < DF_CB; ++cb) h[cb][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw, eb[cb][s], h[cb][mt], 0, 0, 0);
-            }
-#pragma unroll
-        for (int cb = 0; cb < DF_CB; ++cb)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) h[cb][mt][r] = softplus_f(h[cb][mt][r]);
-        // ---- layer 2: 32 -> 32
-        dfx4 h2[DF_CB][2];
-#pragma unroll
-        for (int cb = 0; cb < DF_CB; ++cb)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) h2[cb][mt][r] = lds[DF_O_B2 + 16 * mt + 4 * g + r];
-#pragma unroll
-        for (int s = 0; s < 8; ++s)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                const float aw = lds[DF_O_W2 + (s * 2 + mt) * 64 + lane];
-#pragma unroll
-                for (int cb = 0; cb < DF_CB; ++cb) h2[cb][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw, h[cb][s >> 2][s & 3], h2[cb][mt], 0, 0, 0);
-            }
-        // ---- head 32 -> 3, 0.05 * tanh; lane j = cb*16+col keeps the result of pair j
-#pragma unroll
-        for (int cb = 0; cb < DF_CB; ++cb) {
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) h2[cb][mt][r] = softplus_f(h2[cb][mt][r]);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float acc = 0.0f;
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) acc = fmaf(lds[DF_O_V + c * 32 + g * 8 + mt * 4 + r], h2[cb][mt][r], acc);
-                acc += __shfl_xor(acc, 16);
-                acc += __shfl_xor(acc, 32);
-                if (g == half * DF_CB + cb) r3[c] = acc + lds[DF_O_B3 + c];
-            }
-        }
-        }
-        if (base + lane < cnt) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float r = 0.05f * tanhf(r3[c]);
-                lx[c * w.lcap + i] = xb[c] + r;                  // tpose = init_bigpose + resd (:111)
-                lr[c * w.lcap + i] = r;
-            }
-        }
-    }
-}
-
-// ---- deformer with per-frame t-slices ---------------------------------------------------------------
-// The deformer's third grid coordinate is frame_dim (uv_deformer.py:33-34): ONE value for the whole call.
-// So per level the z corner pair and its weight are the same for every point, and the 3-D grid collapses
-// to a 2-D (u,v) table  S_l[cx][cy] = (1-tz) row(cx,cy,c0z) + tz row(cx,cy,c1z)  (hashed levels included:
-// the slice of a hashed level is materialised densely).  sum_l res_l^2 = 2959 entries (24 KB) for the
-// reference's 8 levels — built once per call by deform_slice_body (k_front_scene) and held in LDS, so the 64 L1-line gathers
-// per pair that bounded the kernel become 32 ds_read_b64.  (u,v) index math stays the reference's.
 struct LaneSlice { int off, res; float cell; };
 
 __device__ __forceinline__ void lane_level_slice(const float2* S, const LaneSlice& L, float x, float y, float& f0, float& f1) {
@@ -401,15 +221,15 @@ __device__ __forceinline__ void lane_level_slice(const float2* S, const LaneSlic
     f1 = fmaf(w11, s11.y, fmaf(w10, s10.y, fmaf(w01, s01.y, w00 * s00.y)));
 }
 
-// The hidden activations of this kernel are kept in the log2 domain, u = log2(1 + exp2(z log2e)) = softplus(z) / ln2, with the two
-// scale factors folded into the staged weights as in the part MLPs (mlp_common.h): a layer that feeds a Softplus is scaled by log2e
-// (weights and bias), a layer that consumes Softplus outputs by ln2 — for the hidden-to-hidden layer the two cancel, only its bias is
-// scaled.  {min, exp2, add, log2} = 4 instructions per value instead of the 7 of softplus_f; 64 values per pair.
-__device__ __forceinline__ float softplus_log2(float a) { return log2_raw(1.0f + exp2_raw(fminf(a, 126.0f))); }
-
-#define DF_WPE 3
-template <bool VSMALL>        // VSMALL: the UV volume qualifies for 24-bit index math (volume_is_small, common.h)
-__global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(DF_WPE, DF_WPE))) void k_deform_pairs_slice(RenderArgs a, Workspace w, GridDev dg, DfSliceInfo si,
+// ONE kernel template; its three instantiations are the launches of launch_warp_pairs.  (Shared at this level on purpose: with the
+// 16-pair tile extracted as a function the compiler simplifies the callee on its own, before it is inlined — `g`, `lane` of unknown
+// range, r3 as memory — and the slice form comes out with 165-168 instead of 152 registers; the body under two __global__ wrappers,
+// or the weight staging as a function of its own, reorder its prologue.  This spelling compiles the slice form to the code of the
+// separate kernel it replaces, byte for byte: profiles/deform_one_statement.md.)
+// Occupancy request: three waves per SIMD for the slice form (152 registers); the 3-D gathers keep more state live — two.
+#define DF_CB 2                         // 16-pair tiles in flight per wave (register budget)
+template <bool SLICE, bool VSMALL>      // VSMALL: the UV volume qualifies for 24-bit index math (volume_is_small, common.h)
+__global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(SLICE ? 3 : 2, SLICE ? 3 : 2))) void k_deform_pairs(RenderArgs a, Workspace w, GridDev dg, DfSliceInfo si,
                                                                  const float* __restrict__ W0, const float* __restrict__ B0,
                                                                  const float* __restrict__ W1, const float* __restrict__ B1,
                                                                  const float* __restrict__ W2, const float* __restrict__ B2) {
@@ -418,10 +238,12 @@ __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(DF_WPE
     const int cnt = w.counters[CNT_PAIRS + p];
     if ((int64_t)blockIdx.x * DF_BLOCK >= cnt) return;
     float2* S = reinterpret_cast<float2*>(lds + DF_LDS);
-    for (int t = threadIdx.x; t < si.off[8]; t += DF_BLOCK) S[t] = w.dslice[t];
+    if constexpr (SLICE)
+        for (int t = threadIdx.x; t < si.off[8]; t += DF_BLOCK) S[t] = w.dslice[t];
+    // the weights in MFMA operand order with the log2-domain scales (deform_mlp.h: DF_O_*)
     for (int t = threadIdx.x; t < 5 * 2 * 64; t += DF_BLOCK) {
         const int ln = t & 63, mt = (t >> 6) & 1, s = t >> 7, g = ln >> 4, i = ln & 15, col = df_col(s, g);
-        lds[DF_O_W1 + t] = col >= 0 ? W0[(16 * mt + i) * 19 + col] * INVR_LOG2E : 0.0f;      // log2-domain activations, see below
+        lds[DF_O_W1 + t] = col >= 0 ? W0[(16 * mt + i) * 19 + col] * INVR_LOG2E : 0.0f;
     }
     for (int t = threadIdx.x; t < 8 * 2 * 64; t += DF_BLOCK) {
         const int ln = t & 63, mt = (t >> 6) & 1, s = t >> 7, g = ln >> 4, i = ln & 15;
@@ -437,16 +259,28 @@ __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(DF_WPE
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
-    LaneSlice LA = {0, 2, 1.0f}, LB = {0, 2, 1.0f};             // levels 2g and 2g+1
+    typename std::conditional<SLICE, LaneSlice, LaneLevel2>::type LA, LB;             // levels 2g and 2g+1
+    if constexpr (SLICE) LA = LB = LaneSlice{0, 2, 1.0f};
+    else LA = LB = LaneLevel2{nullptr, 2, 1.0f, false};
 #pragma unroll
     for (int l = 0; l < 8; ++l) {
-        const LaneSlice t = {si.off[l], dg.res[l], dg.cell[l]};
+        decltype(LA) t;
+        if constexpr (SLICE) {
+            t = LaneSlice{si.off[l], dg.res[l], dg.cell[l]};
+        } else {
+            t.hashed = l >= dg.start_hash;
+            t.res = dg.res[l];
+            t.cell = dg.cell[l];
+            const float* tb = dg.separate_dense ? (t.hashed ? dg.hash + (int64_t)(l - dg.start_hash) * dg.T * 2 : dg.dense + dg.dense_off[l] * 2)
+                                                : dg.hash + (int64_t)l * dg.T * 2;
+            t.tab = reinterpret_cast<const float2*>(tb);
+        }
         if (l == 2 * g) LA = t;
         if (l == 2 * g + 1) LB = t;
     }
     const float gb0 = dg.bounds[0], gb1 = dg.bounds[1], gb2 = dg.bounds[2];
     const float ge0 = dg.bounds[3] - gb0, ge1 = dg.bounds[4] - gb1, ge2 = dg.bounds[5] - gb2;
-    const float tn = (a.scene.frame_dim[0] - gb2) / ge2;
+    const float tn = (a.scene.frame_dim[0] - gb2) / ge2;                 // uvt[2] = frame_dim, normalised (:112)
     float* lx = w.l_x[p];
     float* lr = w.l_r[p];
 
@@ -465,11 +299,17 @@ __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(DF_WPE
             for (int cb = 0; cb < DF_CB; ++cb) {
                 const int src = (half * DF_CB + cb) * 16 + col;
                 const float uu = __shfl(un, src), vv = __shfl(vn, src);
-                lane_level_slice(S, LA, uu, vv, eb[cb][0], eb[cb][1]);
-                lane_level_slice(S, LB, uu, vv, eb[cb][2], eb[cb][3]);
+                if constexpr (SLICE) {
+                    lane_level_slice(S, LA, uu, vv, eb[cb][0], eb[cb][1]);
+                    lane_level_slice(S, LB, uu, vv, eb[cb][2], eb[cb][3]);
+                } else {
+                    lane_level_f2(dg, LA, uu, vv, tn, eb[cb][0], eb[cb][1]);
+                    lane_level_f2(dg, LB, uu, vv, tn, eb[cb][2], eb[cb][3]);
+                }
                 eb[cb][4] = g == 0 ? uu : (g == 1 ? vv : (g == 2 ? tn : 0.0f));
             }
-            dfx4 h[DF_CB][2];
+            // ---- layer 1: 20 -> 32
+            f32x4 h[DF_CB][2];
 #pragma unroll
             for (int cb = 0; cb < DF_CB; ++cb)
 #pragma unroll
@@ -487,10 +327,9 @@ __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(DF_WPE
 #pragma unroll
             for (int cb = 0; cb < DF_CB; ++cb)
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h[cb][mt][r] = softplus_log2(h[cb][mt][r]);
-            dfx4 h2[DF_CB][2];
+                for (int mt = 0; mt < 2; ++mt) h[cb][mt] = softplus4_log2(h[cb][mt]);
+            // ---- layer 2: 32 -> 32
+            f32x4 h2[DF_CB][2];
 #pragma unroll
             for (int cb = 0; cb < DF_CB; ++cb)
 #pragma unroll
@@ -505,12 +344,11 @@ __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(DF_WPE
 #pragma unroll
                     for (int cb = 0; cb < DF_CB; ++cb) h2[cb][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(aw, h[cb][s >> 2][s & 3], h2[cb][mt], 0, 0, 0);
                 }
+            // ---- head 32 -> 3; lane j = cb*16+col keeps the result of pair j
 #pragma unroll
             for (int cb = 0; cb < DF_CB; ++cb) {
 #pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h2[cb][mt][r] = softplus_log2(h2[cb][mt][r]);
+                for (int mt = 0; mt < 2; ++mt) h2[cb][mt] = softplus4_log2(h2[cb][mt]);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     float acc = 0.0f;
@@ -631,37 +469,29 @@ int launch_warp_pairs(const RenderArgs& a, const Workspace& w, const GridDev& dg
     int64_t dtiles = cdiv(w.lcap, DF_BLOCK);
     unsigned dgx = (unsigned)(dtiles < 512 ? (dtiles > 0 ? dtiles : 1) : 512);
     DfSliceInfo si;
-    if (deform_slices_fit(dg, si)) {                 // slices built by k_front_scene
-        const size_t lds_bytes = (size_t)DF_LDS * sizeof(float) + (size_t)si.off[8] * sizeof(float2);
-        auto kern = volume_is_small(a.scene.tuv) ? k_deform_pairs_slice<true> : k_deform_pairs_slice<false>;
-        hipLaunchKernelGGL(kern, dim3(dgx, INVR_NUM_PARTS), dim3(DF_BLOCK), lds_bytes, st, a, w, dg, si, dm.w[0], dm.b[0],
-                           dm.w[1], dm.b[1], dm.w[2], dm.b[2]);
-        INVR_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(k_deform_pairs, dim3(dgx, INVR_NUM_PARTS), dim3(DF_BLOCK), 0, st, a, w, dg, dm.w[0], dm.b[0], dm.w[1],
-                       dm.b[1], dm.w[2], dm.b[2]);
+    const bool fit = deform_slices_fit(dg, si);      // slices built by k_front_scene
+    const size_t lds_bytes = (size_t)DF_LDS * sizeof(float) + (fit ? (size_t)si.off[8] * sizeof(float2) : 0);
+    auto kern = !fit ? k_deform_pairs<false, false> : volume_is_small(a.scene.tuv) ? k_deform_pairs<true, true> : k_deform_pairs<true, false>;
+    hipLaunchKernelGGL(kern, dim3(dgx, INVR_NUM_PARTS), dim3(DF_BLOCK), lds_bytes, st, a, w, dg, si, dm.w[0], dm.b[0], dm.w[1], dm.b[1],
+                       dm.w[2], dm.b[2]);
     INVR_LAUNCH_CHECK();
     return 0;
 }
 
 // ---- stand-alone deformer on arbitrary canonical points (invr_deform_fwd) ------------------------
-__global__ __launch_bounds__(WARP_BLOCK) void k_deform_points(SceneDev s, GridDev dg, const float* __restrict__ W0,
-                                                              const float* __restrict__ B0, const float* __restrict__ W1,
-                                                              const float* __restrict__ B1, const float* __restrict__ W2,
-                                                              const float* __restrict__ B2, const float* __restrict__ pts,
-                                                              int64_t n, float* __restrict__ out) {
+__global__ __launch_bounds__(WARP_BLOCK) void k_deform_points(SceneDev s, GridDev dg, MlpDev dm, const float* __restrict__ pts, int64_t n,
+                                                              float* __restrict__ out) {
     int64_t i = (int64_t)blockIdx.x * WARP_BLOCK + threadIdx.x;
     if (i >= n) return;
-    float xb[3] = {pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]}, r[3];
-    deform_point(s, dg, W0, B0, W1, B1, W2, B2, xb, r);
-    out[i * 3] = r[0]; out[i * 3 + 1] = r[1]; out[i * 3 + 2] = r[2];
+    float xb[3] = {pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]}, uvt[3];
+    DeformAct a;
+    deform_fwd_act<false>(s, dg, dm, xb, uvt, a);
+    out[i * 3] = 0.05f * a.th[0]; out[i * 3 + 1] = 0.05f * a.th[1]; out[i * 3 + 2] = 0.05f * a.th[2];
 }
 
 int launch_deform_points(const SceneDev& s, const GridDev& dg, const MlpDev& dm, const float* pts, int64_t n, float* out, hipStream_t st) {
     if (n == 0) return 0;
-    hipLaunchKernelGGL(k_deform_points, dim3((unsigned)cdiv(n, WARP_BLOCK)), dim3(WARP_BLOCK), 0, st, s, dg, dm.w[0], dm.b[0],
-                       dm.w[1], dm.b[1], dm.w[2], dm.b[2], pts, n, out);
+    hipLaunchKernelGGL(k_deform_points, dim3((unsigned)cdiv(n, WARP_BLOCK)), dim3(WARP_BLOCK), 0, st, s, dg, dm, pts, n, out);
     INVR_LAUNCH_CHECK();
     return 0;
 }

@@ -868,11 +868,7 @@ def test_scene_prep_on_device(small_setup):
         check_parts_against_golden(tag, pp.cpu().numpy(), pb.cpu().numpy(), l2.cpu().numpy(), bd.cpu().numpy(), gp)
 
 
-def test_pair_deformer_matches_point_deformer(gpu_setup):
-    """The pair-list deformer of the render pipeline (MFMA MLP, per-frame t-slices of the grid held in LDS)
-    against the thread-per-point deformer behind Network.resd (3-D grid lookups, VALU MLP), which
-    test_warp_deform pins to the reference goldens."""
-    cfg, sd, batch, gb, net = gpu_setup
+def _check_pair_deformer(cfg, gb, net):
     ro, rd, nr, fr = (gb[k][0] for k in ('ray_o', 'ray_d', 'near', 'far'))
     out = net.render_rays(gb, ro, rd, nr, fr, cfg.N_samples)
     torch.cuda.synchronize()
@@ -884,10 +880,38 @@ def test_pair_deformer_matches_point_deformer(gpu_setup):
         r_pairs = v['l_r'][p][:, :c].t().contiguous()
         xb = (v['l_x'][p][:, :c].t() - r_pairs).contiguous()                # init_bigpose up to 1 ulp
         r_pts = net.resd(xb[None], gb)[0]
+        print('PAIRDEFORM part %d pairs %d max|pair - point| %.3g max|resd| %.3g' % (p, c, maxerr(r_pairs, r_pts), float(r_pairs.abs().max())))
         assert maxerr(r_pairs, r_pts) < 1e-6, p
         assert float(r_pairs.abs().max()) <= 0.05 and float(r_pairs.abs().max()) > 1e-4
         n_checked += c
     assert n_checked > 1000
+
+
+def test_pair_deformer_matches_point_deformer(gpu_setup):
+    """The pair-list deformer of the render pipeline (MFMA MLP, per-frame t-slices of the grid held in LDS)
+    against the thread-per-point deformer behind Network.resd (3-D grid lookups, VALU MLP), which
+    test_warp_deform pins to the reference goldens."""
+    cfg, sd, batch, gb, net = gpu_setup
+    _check_pair_deformer(cfg, gb, net)
+
+
+def test_pair_deformer_fallback_matches_point_deformer(gpu_setup, golden):
+    """The same on a deformer grid whose t-slices do NOT fit the LDS budget (encoder_cases' `deformer-small`: b = 1.5, res 4 .. 68,
+    8251 float2 > DF_SLICE_MAX), so that the pair-list deformer gathers from the 3-D tables instead: the other instantiation of the
+    one MFMA kernel body.  Same bars as the slice form: the MLP arithmetic is the same, and the Softplus forms agree to < 2e-7
+    (DESIGN.md, Numerics)."""
+    from invr.config import make_cfg
+    from tests import encoder_cases as EC
+    from tests.test_gpu_deform_bwd import slices_fit
+    _, _, _, gb, _ = gpu_setup
+    meta = dict(zip(golden['meta_keys'].tolist(), golden['meta_vals'].tolist()))
+    grid = dict(EC.SPECS['deformer-small'], include_input=True, use_batch_bounds=False)
+    cfg = make_cfg(table_log2=int(meta['table_log2']), N_samples=int(meta['n_samples']), tpose_deformer={'embedder': {'kwargs': grid}})
+    spec = params.deformer_grid_spec(cfg)
+    assert not slices_fit(spec) and sum(r * r for r in spec['res']) == 8251
+    net = Network(cfg=cfg)
+    net.load_state_dict(params.init_state_dict(cfg, seed=5), strict=True)
+    _check_pair_deformer(cfg, gb, net.to(DEV).eval())
 
 
 def test_fused_adam_matches_torch_adam():

@@ -1,7 +1,7 @@
 """GPU, BASELINE full size: the kernels the frame actually spends its time in, pinned DIRECTLY.
 
 `invr_render_fwd` runs `k_knn_pairs` (cluster / sub-cluster / lattice-cell pruned 4-NN with placeholder-seeded
-top-4), `k_warp_pairs` + `k_deform_pairs_slice` (pre-blended per-vertex matrices, MFMA deformer on per-frame
+top-4), `k_warp_pairs` + `k_deform_pairs` (pre-blended per-vertex matrices, MFMA deformer on per-frame
 t-slices) and `k_part_encode_rs_xcd` (row-sum tables, XCD-partitioned level groups).  The stage entry points of
 include/invr.h run other kernels (brute force / dense / generic), which tests/test_gpu_parity.py pins to the
 reference goldens.  Here the production kernels' own per-pair results are read out of the workspace
@@ -210,7 +210,7 @@ def test_warp_pairs_and_slice_deformer_vs_dense_whole_frame(fr):
         ex = (xb - (tp[slots, p] - rs[slots, p])).abs().max(1)[0]
         ed = (d - td[slots, p]).abs().max(1)[0]
         # residual: 0.05 tanh(MLP(grid(uv(x)))) is steep in x (nearest-vertex UV volume: d uv / d x ~ 40 / m), so it is
-        # compared on the SAME canonical point: MFMA + per-frame t-slices (k_deform_pairs_slice) vs the thread-per-point
+        # compared on the SAME canonical point: MFMA + per-frame t-slices (k_deform_pairs) vs the thread-per-point
         # deformer with 3-D lookups (invr_deform_fwd, pinned to the reference goldens by test_warp_deform)
         r_pts = f['net'].resd(xb[None], ctx)[0]
         er = (r - r_pts).abs().max(1)[0]

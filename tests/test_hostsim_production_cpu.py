@@ -1,4 +1,4 @@
-"""CPU: the PRODUCTION kernels of the eval frame (k_knn_pairs, k_warp_pairs + k_deform_pairs_slice, k_part_encode_rs_xcd, k_part_occ_all /
+"""CPU: the PRODUCTION kernels of the eval frame (k_knn_pairs, k_warp_pairs + k_deform_pairs, k_part_encode_rs_xcd, k_part_occ_all /
 k_winner_lists / k_part_rgb_all) pinned directly — the test bodies of tests/test_gpu_production_kernels.py on a reduced frame
 (96 x 96 pixels x 64 samples, 2^12-row tables) through the host build of the kernel sources (tests/hostsim).  The frame is large
 enough for several 4096-slot groups (segmented pair / winner lists, the colour kernel's segment cursor) and for every class of the
