@@ -304,6 +304,14 @@ size_t invr_part_encode_workspace(int64_t n);
 int invr_part_encode_fwd(const InvrGrid* grid, const float* xyz, int64_t n, int32_t kernel, float* out,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* The five part grids in ONE encoder launch, as a frame issues it: kernel 0 = the XCD-partitioned row-sum kernel (every grid needs
+ * row_sums), 1 = the 64-byte-row kernel with one grid row of workgroups per part.  grids[5]; x_soa[5]: HOST array of DEVICE SoA
+ * point lists (3, stride); counts: DEVICE int32[5], counts[p] <= cap <= stride; emb_soa[5]: HOST array of DEVICE SoA outputs
+ * (20, cap) = rows 0-2 the normalised xyz, 3-18 the level sums, row 19 = 0.  Only the columns below a part's count are read or
+ * written; the lists of a part with count 0 are not touched. */
+int invr_part_encode_fwd_all(const InvrGrid* grids, const float* const* x_soa, int64_t stride, const int32_t* counts,
+                             int64_t cap, int32_t kernel, float* const* emb_soa, void* stream);
+
 /* Deformer.forward without flag (uv_deformer.py:31-38; Network.resd, inb_part_network_multiassign.py:122-124):
  * canonical points (n,3) -> residual (n,3).  Uses scene->tuv/tbounds/frame_dim only. */
 int invr_deform_fwd(const InvrScene* scene, const InvrModel* model, const float* pts, int64_t n, float* resd,

@@ -128,6 +128,7 @@ def _signatures():
         'invr_part_field_fwd': (C.c_int, [model, i32, vp, vp, vp, i64, vp, vp, size, vp]),
         'invr_part_encode_workspace': (size, [i64]),
         'invr_part_encode_fwd': (C.c_int, [grid, vp, i64, i32, vp, vp, size, vp]),
+        'invr_part_encode_fwd_all': (C.c_int, [grid, C.POINTER(vp), i64, vp, i64, i32, C.POINTER(vp), vp]),
         'invr_deform_fwd': (C.c_int, [scene, model, vp, i64, vp, vp]),
         'invr_distortion_fwd': (C.c_int, [vp, vp, i64, i32, vp, vp]),
         'invr_composite_fwd': (C.c_int, [vp, i64, i32, vp, vp, vp, vp]),

@@ -690,6 +690,27 @@ extern "C" int invr_part_encode_fwd(const InvrGrid* grid, const float* xyz, int6
     return 0;
 }
 
+// The five-part encoder launches exactly as a frame issues them (render_impl): kernel 0 = k_part_encode_rs_xcd, 1 =
+// k_part_encode_rows_all.  Everything stays in the frame's SoA form — no staging copies, the counts are read on the device.
+extern "C" int invr_part_encode_fwd_all(const InvrGrid* grids, const float* const* x_soa, int64_t stride, const int32_t* counts,
+                                        int64_t cap, int32_t kernel, float* const* emb_soa, void* stream) {
+    INVR_CHECK(grids && x_soa && counts && emb_soa, "invr_part_encode_fwd_all: null pointer");
+    INVR_CHECK(kernel == 0 || kernel == 1, "invr_part_encode_fwd_all: kernel must be 0 (row sums, XCD) or 1 (64-byte rows)");
+    INVR_CHECK(cap >= 0 && cap <= stride && cap < (1ll << 31), "invr_part_encode_fwd_all: 0 <= cap <= stride required");
+    if (cap == 0) return 0;
+    EncodeAllArgs ea;
+    for (int p = 0; p < INVR_NUM_PARTS; ++p) {
+        INVR_CHECK(x_soa[p] && emb_soa[p], "invr_part_encode_fwd_all: null list of part %d", p);
+        if (check_grid(&grids[p], "part grid")) return 1;
+        INVR_CHECK(kernel == 1 || grids[p].row_sums, "invr_part_encode_fwd_all: the row-sum kernel needs grid->row_sums (invr_grid_row_sums)");
+        ea.g[p] = make_grid_dev(&grids[p]);
+        if (kernel == 1) ea.g[p].row_sums = nullptr;
+        ea.xs[p] = x_soa[p]; ea.emb[p] = emb_soa[p];
+    }
+    ea.counts = counts; ea.stride = stride; ea.cap = cap;
+    return kernel == 0 ? launch_part_encode_all(ea, (hipStream_t)stream) : launch_part_encode_rows_all(ea, (hipStream_t)stream);
+}
+
 extern "C" int invr_deform_fwd(const InvrScene* scene, const InvrModel* model, const float* pts, int64_t n, float* resd,
                                void* stream) {
     INVR_CHECK(scene && model && (n == 0 || (pts && resd)), "invr_deform_fwd: null pointer");

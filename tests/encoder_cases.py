@@ -27,11 +27,22 @@ SPECS = {
     'part-small-noinput': dict(_PART, log2_hashmap_size=12, include_input=False),
     'deformer-small-noinput': dict(_D2, log2_hashmap_size=10, include_input=False),
 }
+# forward-only families (tests/test_gpu_encoder_fwd.py), beside the ones above: kept out of SPECS, whose every member the backward
+# tests build full-size float64 gradient tables for
+SPECS_FWD = {
+    'part-base16': dict(_PART, base_resolution=16, log2_hashmap_size=16),  # level 0 = 16^3 = 4096 rows: the whole LDS stage (the body's case)
+    'part-t9': dict(_PART, log2_hashmap_size=9),                          # T 521 < 1024: the fp64 modulo inside the part kernels
+    'part-t19': dict(_PART, log2_hashmap_size=19),                        # T 2^19 + 21: the two-round 24-bit modulo under the x-delta fold
+    'part-t20': dict(_PART, log2_hashmap_size=20),                        # T 2^20 + 7: the production constants of the one-round modulo
+}
+BBOX_OF = {'part-base16': [[-1, -1.2, -0.34], [0.8, 0.7, 0.5]]}           # the body's box (config.DEFAULTS); every other family: BBOX.  (In BBOX no
+#                                                                           fp32 z reaches c1 - c0 == 2 on the three dense levels of this family.)
+BIG_TABLES = ('part-t19', 'part-t20')                                     # 134 / 336 MB of fp32 tables: n <= 1000, never on the wave machine's default run
 CLOUDS = ('uniform', 'far', 'inside', 'rays', 'one', 'faces')
 
 
 def make_spec(tag):
-    return O.embedder_geometry(bbox=BBOX, **SPECS[tag])
+    return O.embedder_geometry(bbox=BBOX_OF.get(tag, BBOX), **(SPECS[tag] if tag in SPECS else SPECS_FWD[tag]))
 
 
 @functools.lru_cache(maxsize=2)
@@ -69,7 +80,11 @@ def _raw_cloud(kind, m, g):
 
 def make_cloud(kind, n, spec, seed=0):
     """-> x (n,3) float32 world coordinates.  Points on cell ties (GR.tie_mask) are removed from the inputs, by the float64 reference
-    alone and before anything runs; at most 1 % of a generated cloud may go that way."""
+    alone and before anything runs; at most 1 % of a generated cloud may go that way (resolutions up to 666; more above, see below)."""
+    if kind == 'ties':
+        return make_ties(n, spec, seed)
+    if kind == 'wrap':
+        return make_wrap(n, spec, seed)
     bounds = spec['bbox']
     b = bounds.double()
     for attempt in range(8):
@@ -89,7 +104,10 @@ def make_cloud(kind, n, spec, seed=0):
         drop = GR.tie_mask(x, bounds, spec, exempt_faces=kind == 'faces')
         if kind == 'one' and drop.float().mean() > 0.01:    # the one location itself sits on a tie: another location
             continue
-        assert drop.float().mean() <= 0.01, (kind, n, float(drop.float().mean()))
+        # (the band is 2^-20 q either side of a node: 3 axes x 2^-19 x res / 2 per level, x 3.6 for the levels below it in b = 1.38 steps
+        #  = 1e-5 res of the finest level — 0.25 % at res 250, 2 % at the 2008 of a base-16 family, which gets 1.5 times that)
+        cap = max(0.01, 1.5e-5 * max(spec['res']))
+        assert drop.float().mean() <= cap, (kind, n, float(drop.float().mean()))
         x = x[~drop][:n].contiguous()
         assert x.shape[0] == n
         return x
@@ -150,7 +168,7 @@ def headroom(val, ref, noise):
     return float((err[m] / den[m]).max()) if m.any() else 0.0
 
 
-def accept(tag, name, val, ref, noise, o32=None, touched=None, report=print):
+def accept(tag, name, val, ref, noise, o32=None, touched=None, report=print, prefix='ENCB'):
     """The acceptance rule, every element, none left out:
         |kernel - exact| <= 8 noise + (c + 4) 2^-24 A + c 2^-126
     (c + 4) 2^-24 A is the rigorous bound of an fp32 sum of c terms in ANY order, each term formed with at most four roundings;
@@ -163,7 +181,7 @@ def accept(tag, name, val, ref, noise, o32=None, touched=None, report=print):
     err = (val.double() - ref.exact).abs()
     K = headroom(val, ref, noise)
     K32 = headroom(o32, ref, noise) if o32 is not None else float('nan')
-    report('ENCB %-44s %-8s K_kernel %.3g K_oracle32 %.3g max|exact| %.3g' % (tag, name, K, K32, float(ref.exact.abs().max()) if val.numel() else 0.0))
+    report(prefix + ' %-44s %-8s K_kernel %.3g K_oracle32 %.3g max|exact| %.3g' % (tag, name, K, K32, float(ref.exact.abs().max()) if val.numel() else 0.0))
     bad = err > allow
     if bad.any():
         i = int((err - allow).argmax())
@@ -175,3 +193,121 @@ def accept(tag, name, val, ref, noise, o32=None, touched=None, report=print):
         zero = zero & ~touched
     assert (val[zero] == 0.0).all(), '%s %s: %d untouched elements are not exactly 0' % (tag, name, int((val[zero] != 0).sum()))
     return K
+
+
+# ---- forward ----------------------------------------------------------------------------------------------------------------------
+TIE_KINDS = ('dense-z', 'hash-x', 'hash-y', 'hash-z', 'integer', 'below', 'above', 'dense-x', 'dense-y')
+
+
+@functools.lru_cache(maxsize=4)
+def _tie_coordinates(res, size, sh, b0, b1, seed):
+    """Per TIE_KIND the fp32 coordinates (axis, value) that show the pattern at some level, found by the reference's arithmetic alone
+    (GR.fp32_cells' per-axis statement): for a level, an axis and an integer k the 8193 floats around b0 + k cell ext are scanned.
+        c1 - c0 == 2   f the largest float below a power-of-two k <= res - 2 (f + 1.0f rounds up): '<dense|hash>-<axis>'
+        f == k, f the float below / above k (any 1 <= k <= res - 2): 'integer', 'below', 'above' — the cell decision at its edge"""
+    g = torch.Generator().manual_seed(500 + seed)
+    found = {k: [] for k in TIE_KINDS}
+    steps = torch.arange(-4096, 4097, dtype=torch.int32)
+    for l, (r, cell) in enumerate(zip(res, size)):
+        cell = torch.tensor(cell, dtype=torch.float32)
+        pow2 = [k for k in (1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024) if k <= r - 2]
+        others = [int(k) for k in torch.randint(1, max(r - 1, 2), (2,), generator=g).tolist() if 1 <= k <= r - 2]
+        for a in range(3):
+            lo, ext = torch.tensor(b0[a], dtype=torch.float32), torch.tensor(b1[a], dtype=torch.float32) - torch.tensor(b0[a], dtype=torch.float32)
+            for k in pow2 + others:
+                centre = (lo.double() + k * cell.double() * ext.double()).float()
+                if abs(float(centre)) < 1e-3:                   # (neighbouring bit patterns would cross zero)
+                    continue
+                xs = (centre.view(torch.int32) + steps).view(torch.float32)
+                f = ((xs - lo) / ext) / cell                    # :112, :115 in fp32
+                c0, c1 = f.long().clamp(0, r - 1), (f + 1.0).long().clamp(0, r - 1)
+                kf = torch.tensor(float(k))
+                if k in pow2:
+                    found[('hash-' if l >= sh else 'dense-') + 'xyz'[a]] += [(a, float(v)) for v in xs[c1 - c0 == 2][:8]]
+                for name, target in (('integer', kf), ('below', torch.nextafter(kf, kf - 1)), ('above', torch.nextafter(kf, kf + 1))):
+                    found[name] += [(a, float(v)) for v in xs[f == target][:1]]
+    return found
+
+
+def make_ties(n, spec, seed=0):
+    """The `ties` cloud -> x (n,3) fp32: point i carries one coordinate of kind TIE_KINDS[i % 9] (its other two coordinates uniform
+    inside the box).  Asserted here, by GR.fp32_cells and before anything runs: at least min(16, n // 9) points with c1 - c0 == 2
+    on the z axis of a dense level and on each of the x, y, z axes of a hashed level."""
+    bounds = spec['bbox']
+    found = _tie_coordinates(tuple(spec['res']), tuple(float(s) for s in spec['size']), spec['start_hash'],
+                             tuple(bounds[0].tolist()), tuple(bounds[1].tolist()), seed)
+    g = torch.Generator().manual_seed(9000 + seed)
+    b = bounds.double()
+    x = (b[0] + torch.rand(n, 3, generator=g, dtype=torch.float64) * (b[1] - b[0])).float()
+    for i in range(n):
+        cand = found[TIE_KINDS[i % len(TIE_KINDS)]]
+        if cand:
+            a, v = cand[(i // len(TIE_KINDS)) % len(cand)]
+            x[i, a] = v
+    cells = GR.fp32_cells(x, bounds, spec)
+    sh = spec['start_hash']
+    two = lambda levels, a: int(torch.stack([cells[l][1][:, a] - cells[l][0][:, a] == 2 for l in levels]).any(0).sum())
+    want = min(16, n // len(TIE_KINDS))
+    counts = {'dense-z': two(range(sh), 2), 'hash-x': two(range(sh, spec['L']), 0), 'hash-y': two(range(sh, spec['L']), 1),
+              'hash-z': two(range(sh, spec['L']), 2)}
+    assert all(v >= want for v in counts.values()), (counts, want)
+    return x.contiguous()
+
+
+def make_wrap(n, spec, seed=0):
+    """The `wrap` cloud -> x (n,3) fp32 inside the box: points of which, at some hashed level, the two x corners of a (y, z) corner
+    pair lie on either side of the table's end — the c1x row is the c0x row + a small delta folded back into [0, T), in both
+    directions.  (x's hash prime is 1: without the modulo the two rows are a few apart, so rows more than T / 2 apart have wrapped.)
+    One point in T / 60 or so of a uniform cloud is one; they are found by the reference's arithmetic alone (GR.fp32_cells,
+    GR.level_rows) among up to 4 M uniform points.  Asserted here: at least min(n, 32) / 4 in each direction; the rest is uniform."""
+    bounds, T, sh, L = spec['bbox'], spec['T'], spec['start_hash'], spec['L']
+    b = bounds.double()
+    g = torch.Generator().manual_seed(7000 + seed)
+    up, down, plain = [], [], None
+    want = max(n // 2, 1)
+    for _ in range(16):
+        x = (b[0] + torch.rand(262144, 3, generator=g, dtype=torch.float64) * (b[1] - b[0])).float()
+        cells = GR.fp32_cells(x, bounds, spec)
+        u = torch.zeros(x.shape[0], dtype=torch.bool)
+        d = torch.zeros_like(u)
+        for l in range(sh, L):
+            rows = GR.level_rows(cells[l][0], cells[l][1], spec, l)
+            for k in range(4):                                  # (rows[k]: the c0x corner, rows[k + 4]: the c1x corner of the same y, z)
+                u |= rows[k] - rows[k + 4] > T // 2
+                d |= rows[k + 4] - rows[k] > T // 2
+        up.append(x[u]); down.append(x[d])
+        plain = x[~(u | d)] if plain is None else plain
+        if sum(map(len, up)) >= want and sum(map(len, down)) >= want:
+            break
+    up, down = torch.cat(up)[:want], torch.cat(down)[:want]
+    need = min(n, 32) // 4
+    assert len(up) >= need and len(down) >= need, (len(up), len(down), need)
+    pick = lambda i: (up, down)[i % 2][i // 2] if i // 2 < len((up, down)[i % 2]) else plain[i]       # up, down, up, ... then uniform
+    return torch.stack([pick(i) for i in range(n)]).contiguous() if n else torch.zeros(0, 3)
+
+
+def oracle_fwd(x, dense, hsh, spec, dtype, chunk=65536):
+    """O.hash_embed in `dtype` (the tables are converted only when `dtype` is not theirs)."""
+    sd = {'e.bounds': spec['bbox'].to(dtype), 'e.entries_size': spec['size'].to(dtype), 'e.entries_num': torch.tensor(spec['res']),
+          'e.entries_sum': spec['entries_sum'], 'e.offsets': GR.corner_offsets().to(dtype), 'e.hash': hsh.to(dtype)}
+    if spec['separate_dense']:
+        sd['e.dense'] = dense.to(dtype)
+    with torch.no_grad():
+        out = [O.hash_embed(x[i:i + chunk].to(dtype), sd, 'e.', spec) for i in range(0, x.shape[0], chunk)]
+    return torch.cat(out, 0) if out else torch.zeros(0, spec['out_dim'], dtype=dtype)
+
+
+def forward_noise(x, dense, hsh, spec, ref, cells, trials=4, seed=0, with_oracle=True):
+    """noise_of's convention for the forward, per element: the larger of (a) the deviation from `exact` of O.hash_embed in fp32 and
+    (b) the largest move of `exact` under `trials` perturbations x + s (|x| + 1) 2^-23, s = +-1 per coordinate, with the cells held.
+    -> noise (n,out_dim), the fp32 oracle's output.  with_oracle False leaves (a) out: the rule the oracle ITSELF is held to on the
+    `ties` cloud (tests/test_grid_reference_cpu.py)."""
+    o32 = oracle_fwd(x, dense, hsh, spec, torch.float32)
+    noise = (o32.double() - ref.exact).abs() if with_oracle else torch.zeros_like(ref.exact)
+    g = torch.Generator().manual_seed(3000 + seed)
+    x64 = x.double()
+    for _ in range(trials):
+        s = torch.randint(0, 2, x64.shape, generator=g).double() * 2.0 - 1.0
+        p = GR.encoder_fwd(x64 + s * (x64.abs() + 1.0) * 2.0 ** -23, dense, hsh, spec['bbox'], spec, cells=cells, companions=False)
+        noise = torch.maximum(noise, (p.exact - ref.exact).abs())
+    return noise, o32

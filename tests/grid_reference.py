@@ -1,6 +1,6 @@
-"""Test infrastructure: float64 reference of the BACKWARD of the multi-resolution hash-grid encoder
-(part_base_embedder.py:106-174 as oracle/nvr_oracle.py:hash_embed restates it), together with its conditioning.  Checker only:
-plain vectorised float64 torch, no import of the product.
+"""Test infrastructure: float64 reference of the BACKWARD (encoder_bwd) and the FORWARD (encoder_fwd, at the end) of the
+multi-resolution hash-grid encoder (part_base_embedder.py:106-174 as oracle/nvr_oracle.py:hash_embed restates it), together with
+its conditioning.  Checker only: plain vectorised float64 torch, no import of the product.
 
 For points x (n,3), an upstream gradient g_out (n,out_dim), the tables, the bounds and a spec (oracle.embedder_geometry) it returns
 per output tensor (g_xyz, g_dense, g_hash) a Ref:
@@ -157,3 +157,85 @@ def tie_mask(x, bounds, spec, exempt_faces=False):
             tie &= ~((xn == 0.0) | (xn == 1.0))
         drop |= tie.any(1)
     return drop
+
+
+# ---- forward --------------------------------------------------------------------------------------------------------------------
+def fp32_cells(x, bounds, spec):
+    """The reference's own DISCRETE decision, in its own fp32 arithmetic as torch evaluates it on the CPU (:112-118): x_n = (x - b0) /
+    (b1 - b0), f = x_n / size_l, trunc(f) and trunc(f + 1), clipped.  Every operation is a correctly rounded IEEE one, so the bits are
+    defined without reference to any kernel.  -> [(c0, c1)] per level, (n,3) int64 each.  Where f lies half an ulp below a
+    power-of-two integer, f + 1 rounds up and c1 = c0 + 2."""
+    b = bounds.float()
+    xn = (x.float() - b[0]) / (b[1] - b[0])
+    cells = []
+    for l in range(spec['L']):
+        res = int(spec['res'][l])
+        f = xn / spec['size'][l].float()
+        cells.append((f.long().clamp(0, res - 1), (f + 1.0).long().clamp(0, res - 1)))
+    return cells
+
+
+_ROW_SUMS = []                                                         # [(dense, hsh, sums, abs sums)]: the last two tables seen
+
+
+def row_sums64(dense, hsh, spec):
+    """Per table row the float64 sum of its F features and of their absolute values, invr_grid_row_sums order -> (rows,), (rows,).
+    (Summed from the fp32 tables directly: a 2^20 + 7 table is never copied to float64.)"""
+    for d, h, s, a in _ROW_SUMS:
+        if d is dense and h is hsh:
+            return s, a
+    parts = [dense, hsh] if spec['separate_dense'] else [hsh]
+    s = torch.cat([p.reshape(-1, spec['F']).sum(1, dtype=torch.float64) for p in parts])
+    a = torch.cat([p.reshape(-1, spec['F']).abs().sum(1, dtype=torch.float64) for p in parts])
+    _ROW_SUMS.append((dense, hsh, s, a))
+    del _ROW_SUMS[:-2]
+    return s, a
+
+
+def encoder_fwd(x, dense, hsh, bounds, spec, cells=None, companions=True):
+    """Float64 forward -> Ref(exact, A, c) of out (n,out_dim).  `cells` (fp32_cells): the corner cells are the reference's discrete
+    fp32 decision and everything continuous — t = f64 - c0, the weights, the sums — is float64; None: the cells of float64 (the two
+    agree on a tie-free cloud).  A = the same sums with |w_k| |table entry|; c (out_dim,) = the number of summands of a column: 8 F for a
+    level summed over features, 8 for a concatenated feature, 8 L for a feature summed over levels.  Input columns: exact = the float64
+    normalised coordinate, A = |x - b0| / |ext|, c = 1.  The rows a point needs are gathered BEFORE widening to float64."""
+    L, F, n = spec['L'], spec['F'], x.shape[0]
+    xn = normalise(x, bounds)
+    rowscalar = spec['sum'] and spec['sum_over_features']
+    if rowscalar:
+        rs, rsa = row_sums64(dense, hsh, spec)
+    sep, sh, dr = spec['separate_dense'], spec['start_hash'], spec['dense_rows']
+    lev, levA = [], []
+    for l in range(L):
+        if cells is None:
+            c0, c1, t = level_cells(xn, spec, l)
+        else:
+            c0, c1 = cells[l]
+            t = xn / spec['size'][l].double() - c0
+        rows = level_rows(c0, c1, spec, l)
+        src, base = (dense.reshape(-1, F), 0) if sep and l < sh else (hsh.reshape(-1, F), dr)
+        o = torch.zeros(n, 1 if rowscalar else F, dtype=torch.float64)
+        oA = torch.zeros_like(o)
+        for k in range(8):
+            w = [t[:, a] if (k >> (2 - a)) & 1 else 1.0 - t[:, a] for a in range(3)]
+            wk = (w[0] * w[1] * w[2])[:, None]
+            if rowscalar:
+                v, va = rs[rows[k]][:, None], rsa[rows[k]][:, None]
+            else:
+                v = src[rows[k] - base].double()
+                va = v.abs()
+            o += wk * v
+            if companions:
+                oA += wk.abs() * va
+        lev.append(o)
+        levA.append(oA)
+    if not spec['sum'] or rowscalar:
+        e, A, c = torch.cat(lev, 1), torch.cat(levA, 1), torch.full((len(lev) * lev[0].shape[1],), 8.0 * (F if rowscalar else 1))
+    else:
+        e, A, c = sum(lev), sum(levA), torch.full((F,), 8.0 * L)
+    if spec['include_input']:
+        b = bounds.double()
+        e = torch.cat([xn, e], 1)
+        A = torch.cat([(x.double() - b[0]).abs() / (b[1] - b[0]).abs(), A], 1)
+        c = torch.cat([torch.ones(3), c])
+    assert e.shape == (n, spec['out_dim'])
+    return Ref(e, A if companions else None, c.double() if companions else None)

@@ -60,7 +60,7 @@ def test_library_exports_header_symbols():
     assert int(re.search(r'#define INVR_ABI_VERSION (\d+)', hdr).group(1)) == _abi.ABI_VERSION
     # every declaration parses as a prototype, and the binding's one table states each with the header's types, in the header's order
     protos = header_prototypes()
-    assert len(protos) == 52
+    assert len(protos) == 53
     assert sorted(name for _, name, _ in protos) == names, 'an invr_ declaration of the header did not parse as a prototype'
     assert [name for _, name, _ in protos] == list(_abi.SIGNATURES) == _abi.EXPORTS
     for ret, name, params in protos:
