@@ -95,6 +95,12 @@ class InvrPerceptualLayout(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ARRAYS + ('n_part1', 'n_part2', 'n_partial', 'bytes')]
 
 
+class InvrMeshLayout(C.Structure):
+    """include/invr_mesh.h: byte offsets of the per-point arrays of one surface extraction in the caller's workspace."""
+    ARRAYS = ('masks', 'tcounts', 'voffsets', 'toffsets', 'counts', 'partials')
+    _fields_ = [(k, C.c_int64) for k in ARRAYS + ('n_points', 'n_blocks', 'bytes')]
+
+
 def _signatures():
     """name -> (restype, argtypes) of every prototype of include/invr.h, in the header's order (tests/test_abi_symbols.py holds each
     entry against the header's text).  vp = any data pointer: device tensors, host arrays and the stream go through as addresses."""
@@ -176,8 +182,22 @@ def _signatures_perceptual():
     }
 
 
+def _signatures_mesh():
+    """The same table for include/invr_mesh.h (tests/test_abi_mesh_cpu.py holds it against that header's text)."""
+    i32, i64, f32, size, vp = C.c_int32, C.c_int64, C.c_float, C.c_size_t, C.c_void_p
+    f3, i3 = f32 * 3, i32 * 3                       # origin / voxel / dims: host arrays
+    return {
+        'invr_grid_points': (C.c_int, [f3, f3, i3, i64, i64, vp, vp]),
+        'invr_mesh_workspace_bytes': (size, [i3]),
+        'invr_mesh_workspace_layout': (C.c_int, [i3, C.POINTER(InvrMeshLayout)]),
+        'invr_mesh_count': (C.c_int, [vp, i3, f32, vp, size, vp, vp]),
+        'invr_mesh_emit': (C.c_int, [vp, i3, f3, f3, f32, vp, size, vp, i64, vp, i64, vp, vp]),
+    }
+
+
 SIGNATURES = _signatures()
 SIGNATURES_PERCEPTUAL = _signatures_perceptual()
+SIGNATURES_MESH = _signatures_mesh()
 EXPORTS = list(SIGNATURES)
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
 BWD_HEAD, BWD_DEFORMER, BWD_ALL = 1, 64, 127
@@ -195,7 +215,7 @@ def lib():
             raise RuntimeError('libinvr.so is not built (%s); run `python -c "import __graft_entry__ as g; g.build()"`. '
                                'There is no CPU fallback for the render path.' % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()):
+        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_MESH.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
         if L.invr_version() != ABI_VERSION:
@@ -283,6 +303,17 @@ def perceptual_views(ws, H, W):
     for k in ('g12', 'gm12', 'g11', 'gm11'):
         v[k] = view(getattr(lay, k), (64, H, W))
     return v
+
+
+def mesh_views(ws, dims):
+    """Zero-copy tensor views of the arrays invr_mesh_count keeps in the workspace `ws` (uint8 tensor) for a volume of `dims`."""
+    lay = InvrMeshLayout()
+    check(lib().invr_mesh_workspace_layout((C.c_int32 * 3)(*dims), C.byref(lay)))
+    n, nb = lay.n_points, lay.n_blocks
+    return {'layout': lay, 'masks': ws[lay.masks:lay.masks + n], 'tcounts': ws[lay.tcounts:lay.tcounts + n],
+            'voffsets': ws[lay.voffsets:lay.voffsets + 4 * n].view(torch.int32), 'toffsets': ws[lay.toffsets:lay.toffsets + 4 * n].view(torch.int32),
+            'counts': ws[lay.counts:lay.counts + 32].view(torch.int64),
+            'partials': ws[lay.partials:lay.partials + 8 * nb].view(torch.int32).view(2, nb)}
 
 
 def perceptual_pack(weights, biases, packed=None):

@@ -81,6 +81,7 @@ DEFAULTS = {
     'fused_perceptual': True,   # training with use_lpips: the perceptual image term on the HIP kernels inside that node (autograd.TrainLossPerceptualFn); False: torch ops
     'train_fused': True,     # training: ONE differentiable node (invr_train_fwd / invr_train_bwd); False: op-by-op autograd graph (autograd.render_train)
     'train_hip_mlp': True,   # training: part MLPs forward + backward on the HIP kernels (False: torch ops, autograd.part_field)
+    'voxel_size': [0.005, 0.005, 0.005],   # lib/config/config.py:88: the grid step of the mesh extraction (invr.mesh)
     'eval_row_sums': True,   # eval-mode renders read the part grids through derived row-sum tables (invr_grid_row_sums)
     # image loss: configs/inb/inb_377.yaml sets use_lpips True (VGG19 from torchvision, absent on this image).  The stand-alone
     # default is the plain MSE; adopt() takes the host's value and NetworkWrapper raises if no perceptual loss can be had.

@@ -5,6 +5,8 @@ they run where the reference is absent (the GPU box):
   train_step    : one optimisation step of Trainer.train (lib/train/trainers/trainer.py:108-149)
   psnr_metric   : Evaluator.psnr_metric / evaluate (lib/evaluators/if_nerf.py:28-31, 80-115): PSNR over
                   the whole HxW image with zeros outside mask_at_box
+  run_mesh      : one surface mesh (.ply) per frame: what the reference's tmesh hooks and visualizer (lib/visualizers/if_nerf.py:133-160)
+                  are for, as the posed mesh (invr.mesh)
   save_model / load_network : the reference's .pth layout {net, optim, scheduler, recorder, epoch}
                   (lib/utils/net_utils.py:461-528) so checkpoints interchange in both directions
 """
@@ -149,6 +151,27 @@ def run_evaluate(net, batches, device='cuda', in_flight=None, renderer=None, kee
         renderer.in_flight = prev_in_flight
         if hasattr(renderer, 'flush'):
             renderer.flush(release=True)
+    return out
+
+
+def run_mesh(net, batches, out_dir, level=0.1, voxel_size=None, view_from=None, device='cuda'):
+    """One surface mesh per batch (invr.mesh.extract_mesh: the posed occupancy field on a cfg.voxel_size grid, marching tetrahedra on
+    the device) written to out_dir/frame{frame_index:04d}_view{cam_ind:04d}.ply, or mesh_{n:04d}.ply for a batch without those keys.
+    -> dict(paths=[...], vertices=[...], triangles=[...]) with the per-frame counts."""
+    from . import mesh
+    os.makedirs(out_dir, exist_ok=True)
+    out = {'paths': [], 'vertices': [], 'triangles': []}
+    for n, batch in enumerate(batches):
+        batch = {k: (v.to(device) if torch.is_tensor(v) and not (k in HOST_KEYS and not v.is_cuda) else v) for k, v in batch.items()}
+        m = mesh.extract_mesh(net, batch, level=level, voxel_size=voxel_size, view_from=view_from)
+        if 'frame_index' in batch and 'cam_ind' in batch:
+            name = 'frame%04d_view%04d.ply' % (int(batch['frame_index'].reshape(-1)[0]), int(batch['cam_ind'].reshape(-1)[0]))
+        else:
+            name = 'mesh_%04d.ply' % n
+        path = mesh.write_ply(os.path.join(out_dir, name), m['vertices'], m['triangles'], m.get('colors'))
+        out['paths'].append(path)
+        out['vertices'].append(int(m['vertices'].shape[0]))
+        out['triangles'].append(int(m['triangles'].shape[0]))
     return out
 
 
