@@ -195,9 +195,18 @@ def _signatures_mesh():
     }
 
 
+def _signatures_batch():
+    """The same table for include/invr_batch.h (tests/test_abi_batch_cpu.py holds it against that header's text)."""
+    i32, vp = C.c_int32, C.c_void_p
+    return {
+        'invr_patch_batch': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, _f32p, _f64p, _f64p, _f64p, _f32p, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    }
+
+
 SIGNATURES = _signatures()
 SIGNATURES_PERCEPTUAL = _signatures_perceptual()
 SIGNATURES_MESH = _signatures_mesh()
+SIGNATURES_BATCH = _signatures_batch()
 EXPORTS = list(SIGNATURES)
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
 BWD_HEAD, BWD_DEFORMER, BWD_ALL = 1, 64, 127
@@ -215,7 +224,8 @@ def lib():
             raise RuntimeError('libinvr.so is not built (%s); run `python -c "import __graft_entry__ as g; g.build()"`. '
                                'There is no CPU fallback for the render path.' % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_MESH.items()):
+        for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_MESH.items())
+                                          + list(SIGNATURES_BATCH.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
         if L.invr_version() != ABI_VERSION:

@@ -86,6 +86,9 @@ DEFAULTS = {
     # image loss: configs/inb/inb_377.yaml sets use_lpips True (VGG19 from torchvision, absent on this image).  The stand-alone
     # default is the plain MSE; adopt() takes the host's value and NetworkWrapper raises if no perceptual loss can be had.
     'use_lpips': False, 'use_ssim': False, 'use_fourier': False, 'use_tv_image': False, 'vgg19_weights': None,
+    # training patches (invr.trainset): the window side of random_crop_image (lib/config/config.py:252) and the semantic mask the crop
+    # rectangle is taken from ('' = the body mask; the training_stages of the INB yamls switch it to 'head' between epochs)
+    'patch_size': 64, 'sample_focus': '',
     'network': {'occ': {'d_hidden': 64, 'n_layers': 1}},
     'viewdir_embedder': {'kwargs': {'res': 4, 'input_dims': 3}},
     'tpose_deformer': {'embedder': {'kwargs': dict(
