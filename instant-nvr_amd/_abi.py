@@ -203,10 +203,19 @@ def _signatures_batch():
     }
 
 
+def _signatures_sample():
+    """The same table for include/invr_sample.h (tests/test_abi_sample_cpu.py holds it against that header's text)."""
+    i32, vp = C.c_int32, C.c_void_p
+    return {
+        'invr_ray_batch': (C.c_int, [vp, vp, vp, vp, i32, i32, vp, i32, _f64p, _f64p, _f64p, _f64p, _f32p, vp, vp, vp, vp, vp, vp, vp]),
+    }
+
+
 SIGNATURES = _signatures()
 SIGNATURES_PERCEPTUAL = _signatures_perceptual()
 SIGNATURES_MESH = _signatures_mesh()
 SIGNATURES_BATCH = _signatures_batch()
+SIGNATURES_SAMPLE = _signatures_sample()
 EXPORTS = list(SIGNATURES)
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
 BWD_HEAD, BWD_DEFORMER, BWD_ALL = 1, 64, 127
@@ -225,7 +234,7 @@ def lib():
                                'There is no CPU fallback for the render path.' % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_MESH.items())
-                                          + list(SIGNATURES_BATCH.items())):
+                                          + list(SIGNATURES_BATCH.items()) + list(SIGNATURES_SAMPLE.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
         if L.invr_version() != ABI_VERSION:

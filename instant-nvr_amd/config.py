@@ -89,6 +89,11 @@ DEFAULTS = {
     # training patches (invr.trainset): the window side of random_crop_image (lib/config/config.py:252) and the semantic mask the crop
     # rectangle is taken from ('' = the body mask; the training_stages of the INB yamls switch it to 'head' between epochs)
     'patch_size': 64, 'sample_focus': '',
+    # plain ray batches (invr.trainset, the branch taken when none of use_lpips / patch_sampling / use_ssim / use_fourier / use_tv_image
+    # is set): sample_ray_h36m's ray count (inb_377.yaml:45) and its class shares (lib/config/config.py:276-277).  The three switches
+    # after them select sampling variants that are not built: plain sampling raises when one is set (check_plain_sampling).
+    'N_rand': 1024, 'body_sample_ratio': 0.5, 'face_sample_ratio': 0.0, 'patch_sampling': False,
+    'prune_using_geo': False, 'train_with_coord': False, 'sample_using_mse': False,
     'network': {'occ': {'d_hidden': 64, 'n_layers': 1}},
     'viewdir_embedder': {'kwargs': {'res': 4, 'input_dims': 3}},
     'tpose_deformer': {'embedder': {'kwargs': dict(
@@ -163,6 +168,22 @@ def validate(c):
     if bool(get('random_bg', False)) and not bool(get('train_fused', True)):
         raise ValueError('invr: unsupported configuration random_bg = True with train_fused = False — the op-by-op training graph is built '
                          'for epsilon 0 only')
+    return c
+
+
+PATCH_FLAGS = ('use_lpips', 'patch_sampling', 'use_ssim', 'use_fourier', 'use_tv_image')          # tpose_dataset.py:421
+UNSUPPORTED_PLAIN = {
+    'prune_using_geo': 'cfg.prune_using_geo (tpose_dataset.py:444-445) doubles the ray count once a latest.npy exists and prunes by it: not built',
+    'train_with_coord': 'cfg.train_with_coord (tpose_dataset.py:397-405): sampling from recorded coordinate files is not built',
+    'sample_using_mse': 'cfg.sample_using_mse (tpose_dataset.py:406-420): sampling by the error map is not built',
+}
+
+
+def check_plain_sampling(c):
+    """Raise ValueError if `c` asks for a variant of the reference's ray sampling that the plain branch here does not implement."""
+    for k, why in UNSUPPORTED_PLAIN.items():
+        if bool(c.get(k, False)):
+            raise ValueError('invr: unsupported configuration %s = %r — %s' % (k, c.get(k), why))
     return c
 
 

@@ -1,20 +1,32 @@
-"""A training set that keeps a sequence on the device and forms every iteration's batch there: the patch branch of the reference's
-dataset (lib/datasets/h36m/tpose_dataset.py:421-441, taken by every INB yaml: use_lpips, patch_size 64, sample_focus switched by the
-training stages) without its per-iteration image I/O, NumPy ray pass, collation and host-to-device copy of the whole dict.
+"""A training set that keeps a sequence on the device and forms every iteration's batch there, without the reference's per-iteration
+image I/O, NumPy ray pass, collation and host-to-device copy of the whole dict.  Two branches of its Dataset.__getitem__:
+the patch branch (lib/datasets/h36m/tpose_dataset.py:421-441, taken by every INB yaml: use_lpips, patch_size 64, sample_focus switched
+by the training stages) and the plain branch (:442-450, taken when none of use_lpips / patch_sampling / use_ssim / use_fourier /
+use_tv_image is set: cfg.N_rand rays drawn from the body mask, the face mask and the projected box by sample_ray_h36m).
 
   add_frame   uploads a frame once: its pixels, its mask and its scene tensors (A, big_A, pbw, ...), and precomputes on the host what the
-              window draw needs (the crop rectangles of crop_image_msk, row prefix counts of the mask's `== 1` pixels).
+              window draw needs (the crop rectangles of crop_image_msk, row prefix counts of the mask's `== 1` pixels).  With `orig_msk`
+              it also prepares plain sampling (invr.raysample): the bound mask, the three pixel classes as bit planes + row prefix
+              counts on the device, and per class member the reference's own mask_at_box decision on the host.
   draw        pure host code: crop_image_msk + random_crop_image (lib/utils/if_nerf/if_nerf_data_utils.py:611-686) with the reference's
               own random draws in its own order -> the window and its float32 intrinsic matrix.
-  train_batch draw + ONE kernel launch (invr_patch_batch, include/invr_batch.h): the window's rays, the ones inside the body's box
-              compacted in pixel order, the pixels and the mask gathered for them.  The batch references the resident scene tensors.
+  draw_rays   pure host code: the sampling loop of sample_ray_h36m (:253-289) with its randint calls in its order -> (class, rank) rows.
+  train_batch patch: draw + ONE kernel launch (invr_patch_batch, include/invr_batch.h): the window's rays, the ones inside the body's
+              box compacted in pixel order, the pixels and the mask gathered for them.  plain: draw_rays + ONE kernel launch
+              (invr_ray_batch, include/invr_sample.h).  The batch references the resident scene tensors.
   batches     the same, `prefetch` batches ahead on a stream the set owns; yielding waits on that batch's event only.
   test_batch  the full-frame eval batch (rays.rays_within_bounds).
 
-Not built (the reference's other sampling branches): the plain sample_ray_h36m branch (:228-310: cv2.fillPoly bound masks and a
-resampling loop whose draws depend on device results), sample_using_mse, train_with_coord, prune_using_hull; image I/O and
-undistortion (the host hands in frames as the reference holds them at tpose_dataset.py:351); a Dataset wrapper for the reference's
-DataLoader."""
+`mode` of the batch calls: 'patch', 'plain', or None = the reference's rule at :421 read from cfg per batch (a frame that was added
+without `orig_msk` can only give patches and does so under None, as before plain sampling existed; mode='plain' raises for it).
+
+The two branches collate differently, as the reference does: a plain batch has coord (1,n,2) int64 (row, col) where a patch has uint8
+(x, y) of the window, occupancy (1,n) uint8 = orig_msk at the pixel where a patch has bool, mask_at_box all True of n entries, and H, W
+of the frame.
+
+Not built (the reference's other sampling branches): sample_using_mse, train_with_coord, prune_using_hull / prune_using_geo (plain
+sampling raises when cfg sets one); image I/O, undistortion and crop_mask_edge (the host hands in frames as the reference holds them at
+tpose_dataset.py:351, and orig_msk as it reads it at :450); a Dataset wrapper for the reference's DataLoader."""
 import contextlib
 import ctypes as C
 from collections import deque
@@ -24,9 +36,12 @@ import torch
 
 from . import _abi
 from . import config as _config
+from . import raysample
 from .config import PART_NAMES
 
 MAX_SIDE = 256          # include/invr_batch.h INVR_PATCH_MAX_SIDE
+MAX_RAYS = 1 << 20      # include/invr_sample.h INVR_RAY_BATCH_MAX
+STAGING = 4             # page-locked buffers the (class, rank) rows of plain batches travel through
 
 
 def bounding_rect(mask):
@@ -79,6 +94,8 @@ class TrainSet:
         self.shared = {}
         self._stream = None                 # the side stream the batches are formed on (created with the first batch)
         self._uploaded = None               # event behind the last upload: the side stream waits on it
+        self._staging, self._staged = [], 0   # the ring of [pinned (cap,2) int32 buffer, event behind its last copy]
+        self._true_rows = None              # mask_at_box of plain batches: constant rows every such batch views
         if shared:
             self.set_shared(shared)
 
@@ -103,11 +120,16 @@ class TrainSet:
         self.shared = {k: self._upload(v) for k, v in shared.items()}
         self._mark_uploaded()
 
-    def add_frame(self, img, msk, K, R, T, scene, sem_masks=None, latent_index=None, frame_index=None, cam_ind=0):
+    def add_frame(self, img, msk, K, R, T, scene, sem_masks=None, latent_index=None, frame_index=None, cam_ind=0, orig_msk=None,
+                  bound_mask=None, face_value=13):
         """img (H,W,3) float32 and msk (H,W) uint8 as the reference holds them at tpose_dataset.py:351 (undistorted, resized, mask_bkgd
         applied; mask values 0 / 1 / 100); K (3,3), R (3,3), T (3,1) the float64 camera (K scaled by cfg.ratio, T in metres); sem_masks
         (5,H,W) in PART_NAMES order; scene: the frame's un-batched item tensors (A, big_A, pbw, pbounds, wbounds, R, Th, ppts, part_pts,
-        part_pbw, lengths2, bounds, ...), `wbounds` among them.  -> the frame's index."""
+        part_pbw, lengths2, bounds, ...), `wbounds` among them.  -> the frame's index.
+        Plain sampling needs orig_msk (H,W) uint8: the mask the reference reads `occupancy` from (tpose_dataset.py:450, crop_mask_edge
+        already applied when cfg.erode_edge).  bound_mask (H,W) of 0 / 1 is the host's get_bound_2d_mask for pixel parity with cv2; by
+        default the set fills the hull of the projected box itself (raysample.bound_mask: may differ from cv2 on the hull's outline).
+        face_value is the mask value of the face class (`msk == 13`)."""
         img, msk = np.array(img, np.float32, order='C'), np.array(msk, np.uint8, order='C')          # copies: the caller may reuse its buffers
         if img.ndim != 3 or img.shape[2] != 3 or msk.shape != img.shape[:2]:
             raise ValueError('add_frame: img must be (H, W, 3) and msk (H, W) (got %s and %s)' % (img.shape, msk.shape))
@@ -133,6 +155,24 @@ class TrainSet:
                 if sm.sum() != 0:                                              # an empty semantic mask falls back to msk (:424)
                     f.crops[name] = _Crop(msk, sm)
         f.has_sem = sem_masks is not None
+        f.classes = None
+        if orig_msk is not None:
+            orig_msk = np.array(orig_msk, np.uint8, order='C')
+            if orig_msk.shape != msk.shape:
+                raise ValueError('add_frame: orig_msk must be (H, W) like msk (got %s)' % (orig_msk.shape,))
+            if bound_mask is None:
+                bound_mask = raysample.bound_mask(f.wbounds, f.K, f.R, f.T, f.H, f.W)
+            else:
+                bound_mask = np.asarray(bound_mask)
+                if bound_mask.shape != msk.shape or not np.isin(bound_mask, (0, 1)).all():
+                    raise ValueError('add_frame: bound_mask must be (H, W) of 0 / 1 as get_bound_2d_mask returns it')
+            f.classes = raysample.FrameClasses(msk, bound_mask, raysample.inside_box(f.H, f.W, f.K, f.R, f.T, f.wbounds), face_value)
+            f.k_inv = np.ascontiguousarray(np.linalg.inv(f.K))                  # get_rays :32, float64
+            f.orig_msk = torch.from_numpy(orig_msk).to(self.device)
+            f.planes = torch.from_numpy(f.classes.planes.view(np.int64)).to(self.device)
+            f.row_prefix = torch.from_numpy(f.classes.row_prefix).to(self.device)
+        elif bound_mask is not None:
+            raise ValueError('add_frame: bound_mask is given without orig_msk: it serves plain sampling only')
         latent_index = f.index if latent_index is None else int(latent_index)
         frame_index = latent_index if frame_index is None else int(frame_index)
         f.img = torch.from_numpy(img).to(self.device)
@@ -188,6 +228,30 @@ class TrainSet:
         K[1, 2] = K[1, 2] - y
         return x_lo + x, y_lo + y, size, size, K.astype(np.float32)
 
+    # ---- the ray draw of the plain branch (host) ----------------------------------------------------------------------------------
+    def draw_rays(self, index, rng=None):
+        """-> sel (n,2) int32 (class, rank): the sampling loop of sample_ray_h36m on frame `index` with the reference's randint calls in
+        its order from rng (None = the global np.random).  n >= cfg.N_rand and rows repeat, as in the reference.  cfg.N_rand,
+        cfg.body_sample_ratio and cfg.face_sample_ratio are read now."""
+        f = self.frames[index]
+        if f.classes is None:
+            raise ValueError('TrainSet: plain sampling on frame %d, which was added without orig_msk' % index)
+        _config.check_plain_sampling(self.cfg)
+        sel = raysample.draw_rays(f.classes, self.cfg.get('N_rand', 1024), self.cfg.get('body_sample_ratio', 0.5),
+                                  self.cfg.get('face_sample_ratio', 0.0), rng, frame=index)
+        if len(sel) > MAX_RAYS:
+            raise ValueError('TrainSet.draw_rays: %d rays are beyond the %d of one invr_ray_batch call' % (len(sel), MAX_RAYS))
+        return sel
+
+    def _mode(self, mode, index):
+        """'patch' or 'plain' for a batch of frame `index`; None = tpose_dataset.py:421 on cfg as it stands now."""
+        if mode is None:
+            patch = any(bool(self.cfg.get(k, False)) for k in _config.PATCH_FLAGS) or self.frames[index].classes is None
+            return 'patch' if patch else 'plain'
+        if mode not in ('patch', 'plain'):
+            raise ValueError("TrainSet: mode must be 'patch', 'plain' or None (got %r)" % (mode,))
+        return mode
+
     # ---- batches --------------------------------------------------------------------------------------------------------------------
     def _side(self):
         if self.device.type != 'cuda':
@@ -228,8 +292,79 @@ class TrainSet:
                 slot.copy_(count)
         return f, o, (w, h), slot, event
 
+    def _stage(self, sel):
+        """The (class, rank) rows on the device, through the next page-locked buffer of the ring (on the side stream).  A buffer is
+        written again only after the copy that last read it has finished."""
+        sel = torch.from_numpy(sel)
+        if self.device.type != 'cuda':
+            return sel, None
+        if len(self._staging) < STAGING:
+            self._staging.append([None, None])
+        entry = self._staging[self._staged % len(self._staging)]
+        self._staged += 1
+        if entry[1] is not None:
+            entry[1].synchronize()
+        if entry[0] is None or entry[0].shape[0] < sel.shape[0]:
+            entry[0] = torch.empty(max(sel.shape[0], 2048), 2, dtype=torch.int32, pin_memory=True)
+        entry[0][:sel.shape[0]].copy_(sel)
+        dev = torch.empty(sel.shape[0], 2, dtype=torch.int32, device=self.device)
+        dev.copy_(entry[0][:sel.shape[0]], non_blocking=True)
+        return dev, entry
+
+    def _submit_plain(self, index, rng):
+        """Draw and launch one plain batch on the side stream.  -> the pending batch; its size is known here."""
+        f = self.frames[index]
+        sel = self.draw_rays(index, rng)
+        n = len(sel)
+        side = self._side()
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            if side is not None and self._uploaded is not None:
+                side.wait_event(self._uploaded)
+            dev = self.device
+            sel_d, entry = self._stage(sel)
+            o = {'ray_d': torch.empty(n, 3, device=dev), 'near': torch.empty(n, device=dev), 'far': torch.empty(n, device=dev),
+                 'rgb': torch.empty(n, 3, device=dev), 'occupancy': torch.empty(n, dtype=torch.uint8, device=dev),
+                 'coord': torch.empty(n, 2, dtype=torch.int64, device=dev)}
+            u8, i32, i64 = torch.uint8, torch.int32, torch.int64
+            st = C.c_void_p(side.cuda_stream) if side is not None else _abi.stream_ptr()
+            _abi.check(_abi.lib().invr_ray_batch(
+                _abi.ptr(f.img), _abi.ptr(f.orig_msk, u8), _abi.ptr(f.planes, i64), _abi.ptr(f.row_prefix, i32), f.H, f.W, _abi.ptr(sel_d, i32), n,
+                dp(f.k_inv), dp(np.ascontiguousarray(f.R)), dp(f.Tr), dp(f.cam_o), f.wbounds.ctypes.data_as(C.POINTER(C.c_float)),
+                _abi.ptr(o['ray_d']), _abi.ptr(o['near']), _abi.ptr(o['far']), _abi.ptr(o['rgb']), _abi.ptr(o['occupancy'], u8),
+                _abi.ptr(o['coord'], i64), st))
+            event = None
+            if side is not None:
+                event = torch.cuda.Event()
+                event.record(side)
+                entry[1] = event
+                sel_d.record_stream(side)
+        return 'plain', f, o, n, event
+
+    def _finish_plain(self, pending):
+        """Collate one pending plain batch: the caller's stream waits on its event; the host does not (n is known)."""
+        _, f, o, n, event = pending
+        if event is not None:
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(event)
+            for t in o.values():
+                t.record_stream(cur)
+        if f.ray_o_rows.shape[0] < n:                                              # constant rows: grown, never shrunk
+            f.ray_o_rows = f.ray_o[None].expand(n, 3).contiguous()
+        if self._true_rows is None or self._true_rows.shape[0] < n:
+            self._true_rows = torch.ones(max(n, 4096), dtype=torch.bool, device=self.device)
+        batch = {'rgb': o['rgb'][None], 'occupancy': o['occupancy'][None], 'coord': o['coord'][None], 'ray_o': f.ray_o_rows[None, :n],
+                 'ray_d': o['ray_d'][None], 'near': o['near'][None], 'far': o['far'][None], 'mask_at_box': self._true_rows[None, :n],
+                 'H': torch.tensor([f.H], dtype=torch.int64), 'W': torch.tensor([f.W], dtype=torch.int64)}
+        batch.update(f.meta)
+        batch.update(self.shared)
+        batch.update(f.scene)
+        return batch
+
     def _finish(self, pending):
         """Join one pending batch (a host wait on ITS event only) and collate it: the first `count` rows of the compact tensors."""
+        if pending[0] == 'plain':
+            return self._finish_plain(pending)
         f, o, (w, h), slot, event = pending
         if event is not None:
             event.synchronize()
@@ -250,31 +385,37 @@ class TrainSet:
     def _slot(self):
         return torch.empty(1, dtype=torch.int32, pin_memory=self.device.type == 'cuda')
 
-    def train_batch(self, index, rng=None):
+    def train_batch(self, index, rng=None, mode=None):
         """One training batch of frame `index`: the reference item's keys, collated (leading batch dimension of 1)."""
+        if self._mode(mode, index) == 'plain':
+            return self._finish(self._submit_plain(index, rng))
         return self._finish(self._submit(index, rng, self._slot()))
 
-    def batches(self, order, rng=None, prefetch=2):
+    def batches(self, order, rng=None, prefetch=2, mode=None):
         """Generator over the batches of the frames in `order`, `prefetch` of them launched ahead on the set's own stream.  Yielding
         waits on the batch's own event on the host and makes the caller's current stream wait on it; the caller's stream is never
         synchronised.  The draws happen in `order`: the sequence of batches does not depend on `prefetch`.  A yielded batch's tensors
-        are its own: it stays valid for as long as the caller holds it."""
+        are its own: it stays valid for as long as the caller holds it.  `mode` is resolved per batch (None: from cfg as it stands then)."""
         prefetch = max(0, int(prefetch))
         slots = deque(self._slot() for _ in range(prefetch + 1))
         queue = deque()
         for index in order:
-            queue.append(self._submit(index, rng, slots.popleft()))
+            if self._mode(mode, index) == 'plain':
+                queue.append(self._submit_plain(index, rng))
+            else:
+                queue.append(self._submit(index, rng, slots.popleft() if slots else self._slot()))
             if len(queue) > prefetch:
                 pending = queue.popleft()
                 batch = self._finish(pending)
-                slots.append(pending[3])
+                if pending[0] != 'plain':
+                    slots.append(pending[3])
                 yield batch
         while queue:
             yield self._finish(queue.popleft())
 
-    def batch_fn(self, order, rng=None, prefetch=2):
+    def batch_fn(self, order, rng=None, prefetch=2, mode=None):
         """-> batch_fn(epoch, index) for driver.train(wrapper, optimizer, batch_fn, ...): the next batch of `order` per call."""
-        it = self.batches(order, rng, prefetch)
+        it = self.batches(order, rng, prefetch, mode)
         return lambda epoch, index: next(it)
 
     def test_batch(self, index):
