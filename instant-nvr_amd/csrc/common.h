@@ -252,22 +252,6 @@ __device__ __forceinline__ uint32_t hash_mod32(uint64_t x, int k, uint32_t c, ui
     v -= (v >= (int32_t)T) ? (int32_t)T : 0;
     return (uint32_t)v;
 }
-struct GridDev;
-__device__ __forceinline__ uint32_t grid_hash_mod(uint64_t x, const GridDev& g);
-
-__device__ __forceinline__ uint32_t hash_mod(uint32_t cx, uint32_t cy, uint32_t cz, int64_t T, double inv_T) {
-    uint64_t x = (uint64_t)cx ^ ((uint64_t)cy * HASH_P1) ^ ((uint64_t)cz * HASH_P2);
-    double xd = (double)x;
-    double q = floor(xd * inv_T);
-    double r = fma(-q, (double)T, xd);
-    if (r < 0.0) r += (double)T;
-    if (r >= (double)T) r -= (double)T;
-    return (uint32_t)r;
-}
-
-// Normalised coordinate -> per-axis clipped corners and fractional offsets of one level
-// (part_base_embedder.py:115-118): f = x / cell; c0 = clip(trunc(f)), c1 = clip(trunc(f + 1));
-// t = f - c0 (may leave [0,1] outside the box -> extrapolation).
 // x / b through the correctly rounded reciprocal y = RN(1 / b) (host-computed): q0 = RN(x y); two Markstein steps
 // r = fma(-q, b, x), q = fma(r, y, q).  The first makes q faithful, the second then yields RN(x / b) — the IEEE quotient, bit for
 // bit (Markstein 1990; excluded on the host: a divisor whose mantissa is all ones; no over/underflow: |x / b| < 2^40 here and an
@@ -295,24 +279,6 @@ __device__ __forceinline__ float div_exact(float x, float b, float y) {
 __device__ __forceinline__ float rcp_for_div(float b) {
     const bool ok = fabsf(b) > 9.6e-7f && fabsf(b) < 1.0e6f && (__float_as_uint(b) & 0x7fffffu) != 0x7fffffu;
     return ok ? 1.0f / b : 0.0f;
-}
-
-__device__ __forceinline__ void level_corners(float x, float cell, float rcell, int res, int& c0, int& c1, float& t) {
-    float f = div_exact(x, cell, rcell);
-    int a = (int)f;              // v_cvt_i32_f32: truncates toward zero (torch .long())
-    int b = (int)(f + 1.0f);
-    c0 = min(max(a, 0), res - 1);
-    c1 = min(max(b, 0), res - 1);
-    t = f - (float)c0;
-}
-
-__device__ __forceinline__ void level_corners(float x, float cell, int res, int& c0, int& c1, float& t) {
-    float f = x / cell;
-    int a = (int)f;              // v_cvt_i32_f32: truncates toward zero (torch .long())
-    int b = (int)(f + 1.0f);
-    c0 = min(max(a, 0), res - 1);
-    c1 = min(max(b, 0), res - 1);
-    t = f - (float)c0;
 }
 
 __device__ __forceinline__ uint32_t grid_hash_mod(uint64_t x, const GridDev& g) {

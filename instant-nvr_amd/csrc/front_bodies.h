@@ -5,6 +5,7 @@
 // 0.56 ms ray shard), launches that follow each other on one stream start back to back — so independent small kernels share a launch.
 #pragma once
 #include "pipeline.h"
+#include "grid_level.h"
 
 #define CULL_BLOCK 256
 #define CULL_PER 4                      // ray-samples per thread
@@ -410,24 +411,15 @@ __device__ __forceinline__ void deform_slice_body(const GridDev& dg, const DfSli
     int l = 0;
     while (e >= si.off[l + 1]) ++l;
     const int res = dg.res[l];
-    const float tn = (frame_dim[0] - dg.bounds[2]) / (dg.bounds[5] - dg.bounds[2]);
+    const float tn = grid_norm(dg, 2, frame_dim[0]);
     int c0z, c1z;
     float tz;
     level_corners(tn, dg.cell[l], res, c0z, c1z, tz);
     const int idx = e - si.off[l], cx = idx / res, cy = idx - cx * res;
     const bool hashed = l >= dg.start_hash;
-    const float* tb = dg.separate_dense ? (hashed ? dg.hash + (int64_t)(l - dg.start_hash) * dg.T * 2 : dg.dense + dg.dense_off[l] * 2)
-                                        : dg.hash + (int64_t)l * dg.T * 2;
-    const float2* tab = reinterpret_cast<const float2*>(tb);
-    unsigned r0, r1;
-    if (hashed) {
-        const uint64_t hxy = (uint64_t)(uint32_t)cx ^ ((uint64_t)(uint32_t)cy * HASH_P1);
-        r0 = grid_hash_mod(hxy ^ ((uint64_t)(uint32_t)c0z * HASH_P2), dg);
-        r1 = grid_hash_mod(hxy ^ ((uint64_t)(uint32_t)c1z * HASH_P2), dg);
-    } else {
-        r0 = ((unsigned)cx * (unsigned)res + (unsigned)cy) * (unsigned)res + (unsigned)c0z;
-        r1 = ((unsigned)cx * (unsigned)res + (unsigned)cy) * (unsigned)res + (unsigned)c1z;
-    }
+    const float2* tab = reinterpret_cast<const float2*>(grid_level_table<2>(dg, l, hashed));
+    const GridRowPair r = grid_row_zpair(dg, hashed, res, c0z, c1z, cx, cy);
+    const unsigned r0 = r.r0, r1 = r.r1;
     const float2 v0 = tab[r0], v1 = tab[r1];
     const float uz = 1.0f - tz;
     out[e] = make_float2(fmaf(tz, v1.x, uz * v0.x), fmaf(tz, v1.y, uz * v0.y));

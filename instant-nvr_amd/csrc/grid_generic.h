@@ -3,7 +3,7 @@
 // grids of the render path use the wave-cooperative kernel in k_encode.hip instead.
 // Semantics: HashEmbedder.forward, lib/networks/embedders/part_base_embedder.py:106-174.
 #pragma once
-#include "common.h"
+#include "grid_level.h"
 
 // rows (in units of table rows, relative to the level's table) and trilinear weights of the 8
 // corners of level l around normalised point x; returns the level's table base pointer.
@@ -18,10 +18,10 @@ __device__ __forceinline__ const float* grid_level_lookup(const GridDev& g, int 
 #pragma unroll
     for (int k = 0; k < 8; ++k) {                           // offsets 000,001,...,111 (x y z, z fastest) :81-88
         const int cx = (k & 4) ? c1[0] : c0[0], cy = (k & 2) ? c1[1] : c0[1], cz = (k & 1) ? c1[2] : c0[2];
-        // weight_k = prod_axis ((1-o) + (2o-1) t)  (:157-158)
-        const float wx = (k & 4) ? t[0] : 1.0f - t[0], wy = (k & 2) ? t[1] : 1.0f - t[1], wz = (k & 1) ? t[2] : 1.0f - t[2];
-        wts[k] = wx * wy * wz;
-        if (hashed) rows[k] = grid_hash_mod((uint64_t)(uint32_t)cx ^ ((uint64_t)(uint32_t)cy * HASH_P1) ^ ((uint64_t)(uint32_t)cz * HASH_P2), g);
+        wts[k] = trilinear_weight(k, t[0], 1.0f - t[0], t[1], 1.0f - t[1], t[2], 1.0f - t[2]);
+        // (the dense arm here and the table base below restate grid_row / grid_level_table in 64-bit / branch form: through the shared
+        //  functions k_train.hip's k_pair_term_fwd and k_deform_bwd, which inline this, compile to other code — profiles/grid_level_rules.md)
+        if (hashed) rows[k] = grid_row(g, true, res, cx, cy, cz);
         else rows[k] = (int64_t)cx * res * res + (int64_t)cy * res + cz;
     }
     if (g.separate_dense) {
@@ -33,7 +33,7 @@ __device__ __forceinline__ const float* grid_level_lookup(const GridDev& g, int 
 
 __device__ __forceinline__ void grid_normalise(const GridDev& g, const float* xyz, float* x) {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) x[a] = (xyz[a] - g.bounds[a]) / (g.bounds[3 + a] - g.bounds[a]);   // :112
+    for (int a = 0; a < 3; ++a) x[a] = grid_norm(g, a, xyz[a]);
 }
 
 // compile-time L, F; sum=False, include_input=True: out = [x(3), level0 feats(F), level1 ...]

@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <vector>
 #include "pipeline.h"
+#include "grid_level.h"
 #include "train.h"
 
 static thread_local char g_err[512] = "";
@@ -806,8 +807,9 @@ extern "C" int invr_pack_parts(const float* ppts, const float* weights, const in
 
 extern "C" int64_t invr_grid_row_sums_len(const InvrGrid* grid) {
     if (!grid || grid->n_levels < 1 || grid->n_levels > INVR_MAX_LEVELS) return 0;
-    GridDev g = make_grid_dev(grid);
-    return g.separate_dense ? g.dense_rows + (int64_t)(g.L - g.start_hash) * g.T : (int64_t)g.L * g.T;
+    int64_t drows, hrows;
+    grid_table_rows(make_grid_dev(grid), drows, hrows);
+    return drows + hrows;
 }
 
 extern "C" int invr_grid_row_sums(const InvrGrid* grid, float* out, void* stream) {
@@ -1107,13 +1109,14 @@ extern "C" int invr_expand_row_grad(const InvrGrid* grid, const float* row_grad,
     INVR_CHECK(grid->sum && grid->sum_over_features, "invr_expand_row_grad: only sum && sum_over_features grids have row-scalar gradients");
     GridDev g = make_grid_dev(grid);
     hipStream_t st = (hipStream_t)stream;
-    const int64_t hrows = (int64_t)(g.separate_dense ? g.L - g.start_hash : g.L) * g.T;
-    if (g.separate_dense && g.dense_rows) {
+    int64_t drows, hrows;
+    grid_table_rows(g, drows, hrows);
+    if (drows) {
         INVR_CHECK(g_dense, "invr_expand_row_grad: g_dense required");
-        hipLaunchKernelGGL(k_expand_row_grad, dim3((unsigned)cdiv(g.dense_rows * g.F, 256)), dim3(256), 0, st, row_grad, g.dense_rows, g.F, g_dense);
+        hipLaunchKernelGGL(k_expand_row_grad, dim3((unsigned)cdiv(drows * g.F, 256)), dim3(256), 0, st, row_grad, drows, g.F, g_dense);
         INVR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_expand_row_grad, dim3((unsigned)cdiv(hrows * g.F, 256)), dim3(256), 0, st, row_grad + g.dense_rows, hrows, g.F, g_hash);
+    hipLaunchKernelGGL(k_expand_row_grad, dim3((unsigned)cdiv(hrows * g.F, 256)), dim3(256), 0, st, row_grad + drows, hrows, g.F, g_hash);
     INVR_LAUNCH_CHECK();
     return 0;
 }

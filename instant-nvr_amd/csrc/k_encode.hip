@@ -50,14 +50,21 @@ __global__ void k_grid_encode_rt(GridDev g, const float* xyz, int64_t n, float* 
 int launch_grid_encode_generic(const GridDev& g, const float* xyz, int64_t n, float* out, hipStream_t st) {
     if (n == 0) return 0;
     if (g.F > 16 || g.L > INVR_MAX_LEVELS) { invr_set_error("grid encoder: F<=16 and L<=16 required"); return 1; }
-    int od = (g.sum ? (g.sum_over_features ? g.L : g.F) : g.L * g.F) + (g.include_input ? 3 : 0);
-    hipLaunchKernelGGL(k_grid_encode_rt, dim3((unsigned)cdiv(n, 128)), dim3(128), 0, st, g, xyz, n, out, od);
+    hipLaunchKernelGGL(k_grid_encode_rt, dim3((unsigned)cdiv(n, 128)), dim3(128), 0, st, g, xyz, n, out, grid_out_dim(g));
     INVR_LAUNCH_CHECK();
     return 0;
 }
 
-int launch_part_encode_bwd(const GridDev& g, const float* xyz, const float* gout, int64_t n, float* g_dense, float* g_hash,
-                           float* g_xyz, hipStream_t st);
+// The one shape rule of the wave-cooperative part-grid kernels (lane = level * 4 + quarter of a 64-byte row, one scalar per level out):
+// 16 levels, sum over features, the input in front; need_F16: the kernel reads 16-float rows; need_row_sums: it reads the row-sum
+// table.  Sets the error text when it fails and `what` names the caller.
+bool part_grid_supported(const GridDev& g, const char* what, bool need_F16, bool need_row_sums) {
+    if (g.L == 16 && (!need_F16 || g.F == 16) && g.sum && g.sum_over_features && g.include_input && (!need_row_sums || g.row_sums)) return true;
+    if (what)
+        invr_set_error("%s supports n_levels=16%s, sum, sum_over_features, include_input%s (got L=%d F=%d)", what,
+                       need_F16 ? ", n_features_per_level=16" : "", need_row_sums ? " with a row-sum table" : "", g.L, g.F);
+    return false;
+}
 
 // ---- generic backward: table gradients (atomic adds) + input gradient ------------------------------
 // Contention control (a 64x64 training patch sends ~1e5 pairs through 8-row coarse levels):
@@ -83,14 +90,13 @@ __global__ __launch_bounds__(BWD_BLOCK) void k_grid_encode_bwd_rt(GridDev g, con
     const bool rowscalar = g.sum && g.sum_over_features;
     const int Fe = rowscalar ? 1 : g.F;                         // accumulated floats per row
     for (int l = 0; l < g.L; ++l) {
-        const bool hashed = l >= g.start_hash;
-        const int64_t level_rows = hashed ? g.T : (int64_t)g.res[l] * g.res[l] * g.res[l];
+        const int64_t level_rows = grid_level_rows(g, l);
         const bool use_lds = level_rows * Fe <= BWD_LDS_FLOATS;             // uniform
         if (use_lds) {
             for (int j = threadIdx.x; j < (int)(level_rows * Fe); j += BWD_BLOCK) sacc[j] = 0.0f;
             __syncthreads();
         }
-        float* gtab_level = nullptr;
+        float* const gtab = grid_level_like(g, l >= g.start_hash, grid_level_table(g, l), g_dense, g_hash);      // gradient table aligned with the level's table
         for (int64_t i = (int64_t)blockIdx.x * BWD_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BWD_BLOCK) {
             float x[3];
             grid_normalise(g, xyz + i * 3, x);
@@ -98,10 +104,6 @@ __global__ __launch_bounds__(BWD_BLOCK) void k_grid_encode_bwd_rt(GridDev g, con
             int64_t rows[8];
             float wts[8];
             const float* tab = grid_level_lookup(g, l, x, rows, wts);
-            float* gtab;                                                    // gradient table aligned with `tab`
-            if (g.separate_dense) gtab = hashed ? g_hash + (tab - g.hash) : g_dense + (tab - g.dense);
-            else gtab = g_hash + (tab - g.hash);
-            gtab_level = gtab;
             int c0, c1;
             float t[3];
             for (int a = 0; a < 3; ++a) level_corners(x[a], g.cell[l], g.res[l], c0, c1, t[a]);
@@ -133,20 +135,15 @@ __global__ __launch_bounds__(BWD_BLOCK) void k_grid_encode_bwd_rt(GridDev g, con
                 for (int a = 0; a < 3; ++a) {
                     const float prev = l == 0 ? (g.include_input ? go[a] : 0.0f) : g_xyz[i * 3 + a];
                     float v = prev + gt[a] / g.cell[l];                      // f = x / cell, t = f - const
-                    if (l == g.L - 1) v = v / (g.bounds[3 + a] - g.bounds[a]);
+                    if (l == g.L - 1) v = v / grid_box(g).e[a];
                     g_xyz[i * 3 + a] = v;
                 }
         }
         if (use_lds) {
             __syncthreads();
-            // all points of a level share the table slice: recompute its base from the level (no point needed)
-            float* base;
-            if (g.separate_dense) base = hashed ? g_hash + (int64_t)(l - g.start_hash) * g.T * g.F : g_dense + g.dense_off[l] * g.F;
-            else base = g_hash + (int64_t)l * g.T * g.F;
-            (void)gtab_level;
             for (int j = threadIdx.x; j < (int)(level_rows * Fe); j += BWD_BLOCK) {
                 const float v = sacc[j];
-                if (v != 0.0f) unsafeAtomicAdd(base + (rowscalar ? (int64_t)j * g.F : (int64_t)j), v);
+                if (v != 0.0f) unsafeAtomicAdd(gtab + (rowscalar ? (int64_t)j * g.F : (int64_t)j), v);
             }
             __syncthreads();
         }
@@ -160,41 +157,6 @@ __global__ void k_expand_rows(float* __restrict__ gtab, int64_t rows, int F) {
     const float v = gtab[r * F];
     if (v != 0.0f)
         for (int f = 1; f < F; ++f) gtab[r * F + f] = v;
-}
-
-int launch_grid_encode_bwd_generic(const GridDev& g, const float* xyz, const float* gout, int64_t n, float* g_dense,
-                                   float* g_hash, float* g_xyz, hipStream_t st, const int32_t* count) {
-    if (n == 0) return 0;
-    int od = (g.sum ? (g.sum_over_features ? g.L : g.F) : g.L * g.F) + (g.include_input ? 3 : 0);
-    const bool fast = g.L == 16 && g.F == 16 && g.sum && g.sum_over_features && g.include_input && !count;
-    if (fast) { if (launch_part_encode_bwd(g, xyz, gout, n, g_dense, g_hash, g_xyz, st)) return 1; }
-    else {
-        static bool attr_set = false;
-        const size_t lds = (size_t)BWD_LDS_FLOATS * sizeof(float);
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void*)k_grid_encode_bwd_rt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                invr_set_error("hipFuncSetAttribute(k_grid_encode_bwd_rt) failed");
-                return 1;
-            }
-            attr_set = true;
-        }
-        int64_t nb = cdiv(n, BWD_BLOCK);
-        hipLaunchKernelGGL(k_grid_encode_bwd_rt, dim3((unsigned)(nb < 256 ? nb : 256)), dim3(BWD_BLOCK), lds, st, g, xyz, gout, n, count, od,
-                           g_dense, g_hash, g_xyz);
-    }
-    INVR_LAUNCH_CHECK();
-    if (g.sum && g.sum_over_features && g.F > 1) {
-        int64_t hrows = (int64_t)(g.separate_dense ? g.L - g.start_hash : g.L) * g.T;
-        hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)cdiv(hrows, 256)), dim3(256), 0, st, g_hash, hrows, g.F);
-        INVR_LAUNCH_CHECK();
-        if (g.separate_dense) {
-            int64_t drows = 0;
-            for (int l = 0; l < g.start_hash; ++l) drows += (int64_t)g.res[l] * g.res[l] * g.res[l];
-            hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)cdiv(drows, 256)), dim3(256), 0, st, g_dense, drows, g.F);
-            INVR_LAUNCH_CHECK();
-        }
-    }
-    return 0;
 }
 
 // ---- wave-cooperative 16x16 part encoder ----------------------------------------------------------
@@ -225,13 +187,22 @@ __device__ __forceinline__ int quad_bcast_i(int v) {
 template <int SRC>
 __device__ __forceinline__ float quad_bcast_f(float v) { return __int_as_float(quad_bcast_i<SRC>(__float_as_int(v))); }
 
-// Issue the 8 row fetches of one point for this lane's level.  The index arithmetic is shared by
+__device__ __forceinline__ LaneLevel lane_level(const GridDev& g, int level, int q) {
+    LaneLevel L;
+    L.res = g.res[level];
+    L.cell = g.cell[level];
+    L.hashed = level >= g.start_hash;
+    L.tab = reinterpret_cast<const float4*>(grid_level_table<16>(g, level, L.hashed)) + q;
+    return L;
+}
+
+// The 8 rows and the 3 fractional offsets of one point in this lane's level.  The index arithmetic is shared by
 // the 4 lanes of a quad (they fetch the 4 quarters of the same rows): lane q does the division /
 // truncation / clipping of axis q (q < 3) and the row index of corners 2q and 2q+1 (the z pair);
 // everything is exchanged with quad-permute DPP moves, so the int64 hash + prime modulo is evaluated
 // exactly once per corner per level instead of four times.
-__device__ __forceinline__ void fetch_point(const GridDev& g, const LaneLevel& L, int q, float x, float y, float z,
-                                            float4* v, float* wts) {
+__device__ __forceinline__ void quad_point_rows(const GridDev& g, const LaneLevel& L, int q, float x, float y, float z,
+                                                unsigned* row, float* t3) {
     int c0, c1;
     float t;
     const float xa = q == 0 ? x : (q == 1 ? y : z);
@@ -239,29 +210,26 @@ __device__ __forceinline__ void fetch_point(const GridDev& g, const LaneLevel& L
     const int c0x = quad_bcast_i<0>(c0), c1x = quad_bcast_i<0>(c1);
     const int c0y = quad_bcast_i<1>(c0), c1y = quad_bcast_i<1>(c1);
     const int c0z = quad_bcast_i<2>(c0), c1z = quad_bcast_i<2>(c1);
-    const float tx = quad_bcast_f<0>(t), ty = quad_bcast_f<1>(t), tz = quad_bcast_f<2>(t);
+    t3[0] = quad_bcast_f<0>(t); t3[1] = quad_bcast_f<1>(t); t3[2] = quad_bcast_f<2>(t);
     // my two corners: k = 2q (z = c0z) and k = 2q+1 (z = c1z); x bit = q>>1, y bit = q&1
-    const int cx = (q & 2) ? c1x : c0x, cy = (q & 1) ? c1y : c0y;
-    unsigned r0, r1;
-    if (L.hashed) {
-        const uint64_t hxy = (uint64_t)(uint32_t)cx ^ ((uint64_t)(uint32_t)cy * HASH_P1);
-        r0 = grid_hash_mod(hxy ^ ((uint64_t)(uint32_t)c0z * HASH_P2), g);
-        r1 = grid_hash_mod(hxy ^ ((uint64_t)(uint32_t)c1z * HASH_P2), g);
-    } else {
-        const unsigned rb = ((unsigned)cx * (unsigned)L.res + (unsigned)cy) * (unsigned)L.res;
-        r0 = rb + (unsigned)c0z;
-        r1 = rb + (unsigned)c1z;
-    }
-    const float ux = 1.0f - tx, uy = 1.0f - ty, uz = 1.0f - tz;
-    unsigned row[8];
+    const GridRowPair r = grid_row_zpair(g, L.hashed, L.res, c0z, c1z, (q & 2) ? c1x : c0x, (q & 1) ? c1y : c0y);
+    const unsigned r0 = r.r0, r1 = r.r1;
     row[0] = (unsigned)quad_bcast_i<0>((int)r0); row[1] = (unsigned)quad_bcast_i<0>((int)r1);
     row[2] = (unsigned)quad_bcast_i<1>((int)r0); row[3] = (unsigned)quad_bcast_i<1>((int)r1);
     row[4] = (unsigned)quad_bcast_i<2>((int)r0); row[5] = (unsigned)quad_bcast_i<2>((int)r1);
     row[6] = (unsigned)quad_bcast_i<3>((int)r0); row[7] = (unsigned)quad_bcast_i<3>((int)r1);
+}
+
+// Issue the 8 row fetches of one point for this lane's level
+__device__ __forceinline__ void fetch_point(const GridDev& g, const LaneLevel& L, int q, float x, float y, float z,
+                                            float4* v, float* wts) {
+    unsigned row[8];
+    float t[3];
+    quad_point_rows(g, L, q, x, y, z, row, t);
+    const float ux = 1.0f - t[0], uy = 1.0f - t[1], uz = 1.0f - t[2];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        // weight_k = prod_axis ((1-o) + (2o-1) t)  (:157-158), offsets 000,001,..,111 (x y z)
-        wts[k] = ((k & 4) ? tx : ux) * ((k & 2) ? ty : uy) * ((k & 1) ? tz : uz);
+        wts[k] = trilinear_weight(k, t[0], ux, t[1], uy, t[2], uz);
         v[k] = L.tab[(size_t)row[k] * 4];                       // 16 floats per row = 4 float4
     }
 }
@@ -280,25 +248,17 @@ __device__ __forceinline__ void encode_rows_part(const GridDev& g, const float* 
                                                  float* __restrict__ emb, float (*semb)[EMB_K][64]) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int level = lane >> 2, q = lane & 3;
-    LaneLevel L;
-    L.res = g.res[level];
-    L.cell = g.cell[level];
-    L.hashed = level >= g.start_hash;
-    const float* tb = g.separate_dense
-        ? (L.hashed ? g.hash + (int64_t)(level - g.start_hash) * g.T * 16 : g.dense + g.dense_off[level] * 16)
-        : g.hash + (int64_t)level * g.T * 16;
-    L.tab = reinterpret_cast<const float4*>(tb) + q;
-    const float b0x = g.bounds[0], b0y = g.bounds[1], b0z = g.bounds[2];
-    const float ex = g.bounds[3] - b0x, ey = g.bounds[4] - b0y, ez = g.bounds[5] - b0z;
+    const LaneLevel L = lane_level(g, level, q);
+    const GridBox box = grid_box(g);
 
     for (int64_t tile = (int64_t)blockIdx.x * ENC_WAVES + wv; tile * 64 < cnt; tile += (int64_t)gridDim.x * ENC_WAVES) {
         const int64_t base = tile * 64;
         const int m = (int)min((int64_t)64, cnt - base);
-        // lane i holds the normalised coordinates of point base+i (:112)
+        // lane i holds the normalised coordinates of point base+i
         const int64_t pi = base + min(lane, m - 1);
-        const float xi = (xs[pi] - b0x) / ex;
-        const float yi = (xs[stride + pi] - b0y) / ey;
-        const float zi = (xs[2 * stride + pi] - b0z) / ez;
+        const float xi = grid_norm(box, 0, xs[pi]);
+        const float yi = grid_norm(box, 1, xs[stride + pi]);
+        const float zi = grid_norm(box, 2, xs[2 * stride + pi]);
         semb[wv][0][lane] = xi; semb[wv][1][lane] = yi; semb[wv][2][lane] = zi;
         semb[wv][EMB_K - 1][lane] = 0.0f;                        // pad column
         for (int j = 0; j < m; j += 2) {
@@ -381,26 +341,21 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
     while (tp > 16 && n / tp < 4096) tp >>= 1;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int level = lane >> 2, q = lane & 3;
-    LaneLevel L;
-    L.res = g.res[level];
-    L.cell = g.cell[level];
-    L.hashed = level >= g.start_hash;
-    const float* tb = g.separate_dense
-        ? (L.hashed ? g.hash + (int64_t)(level - g.start_hash) * g.T * 16 : g.dense + g.dense_off[level] * 16)
-        : g.hash + (int64_t)level * g.T * 16;
+    const LaneLevel L = lane_level(g, level, q);
+    const float* tb = reinterpret_cast<const float*>(L.tab - q);
     // gradient base of my level + stride between rows: full-size table (column 0 of a 16-float row) or compact row scalars
     float* gtb;
     int gstride;
     if (io.rowgrad) {
-        gtb = io.rowgrad + (g.separate_dense ? (L.hashed ? g.dense_rows + (int64_t)(level - g.start_hash) * g.T : g.dense_off[level])
-                                             : (int64_t)level * g.T);
+        gtb = io.rowgrad + grid_level_rs_off(g, level, L.hashed);
         gstride = 1;
     } else {
+        // = grid_level_like(g, L.hashed, tb, io.g_dense, io.g_hash), restated: the shared form changes this kernel's code
         gtb = g.separate_dense ? (L.hashed ? io.g_hash + (tb - g.hash) : io.g_dense + (tb - g.dense)) : io.g_hash + (tb - g.hash);
         gstride = 16;
     }
-    L.tab = reinterpret_cast<const float4*>(tb) + q;
-    // LDS slot of my level (small dense levels only), laid out back to back
+    // LDS slot of my level.  The small levels lie back to back in ssmall: a dense level of a separate_dense grid (contiguous in g_dense
+    // from dense_off[l]) of at most BWD_SMALL_ROWS rows that still fits behind the ones before it
     int small_off = -1, small_total = 0;
     for (int l = 0; l < 16; ++l) {
         const int64_t rows = (int64_t)g.res[l] * g.res[l] * g.res[l];
@@ -412,8 +367,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
     for (int j = threadIdx.x; j < BWD_CACHE; j += ENC_BLOCK) { ckey[j] = 0xFFFFFFFFu; cval[j] = 0.0f; }
     const bool cached = small_off < 0 && !L.hashed && g.separate_dense && L.res <= BWD_CACHE_RES;
     __syncthreads();
-    const float b0x = g.bounds[0], b0y = g.bounds[1], b0z = g.bounds[2];
-    const float ex = g.bounds[3] - b0x, ey = g.bounds[4] - b0y, ez = g.bounds[5] - b0z;
+    const GridBox box = grid_box(g);
 
     // a wave walks the tp (<= 64) points of its tile one after the other (all 64 lanes on one point): a training
     // patch has only ~3e4 pairs per part, so the tile shrinks until the grid fills the GPU
@@ -421,8 +375,8 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
         const int64_t base = tile * tp;
         const int m = (int)min((int64_t)tp, n - base);
         const int64_t pi = base + min(lane, m - 1);
-        const float xi = (io.xyz[pi * io.x_ps] - b0x) / ex, yi = (io.xyz[pi * io.x_ps + io.x_cs] - b0y) / ey,
-                    zi = (io.xyz[pi * io.x_ps + 2 * io.x_cs] - b0z) / ez;
+        const float xi = grid_norm(box, 0, io.xyz[pi * io.x_ps]), yi = grid_norm(box, 1, io.xyz[pi * io.x_ps + io.x_cs]),
+                    zi = grid_norm(box, 2, io.xyz[pi * io.x_ps + 2 * io.x_cs]);
         if (io.go_cs == 1) {
             for (int e = lane; e < m * 19; e += 64) sgo[wv][e / 19][e % 19] = io.gout[base * io.go_ps + e];      // coalesced AoS tile copy
         } else if (lane < m) {
@@ -447,33 +401,8 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
             }
             unsafeAtomicAdd(gtb + (size_t)r * gstride, vsum);               // column 0 = row scalar
         };
-        // the rows and corner weights of point j (quad-shared index math), and its eight row quarters
-        auto prep = [&](int j, unsigned* row, float* tq) {
-            const float x = rdlane(xi, j), y = rdlane(yi, j), z = rdlane(zi, j);
-            int c0, c1;
-            float t;
-            const float xa = q == 0 ? x : (q == 1 ? y : z);
-            level_corners(xa, L.cell, L.res, c0, c1, t);
-            const int c0x = quad_bcast_i<0>(c0), c1x = quad_bcast_i<0>(c1);
-            const int c0y = quad_bcast_i<1>(c0), c1y = quad_bcast_i<1>(c1);
-            const int c0z = quad_bcast_i<2>(c0), c1z = quad_bcast_i<2>(c1);
-            tq[0] = quad_bcast_f<0>(t); tq[1] = quad_bcast_f<1>(t); tq[2] = quad_bcast_f<2>(t);
-            const int cx = (q & 2) ? c1x : c0x, cy = (q & 1) ? c1y : c0y;
-            unsigned r0, r1;
-            if (L.hashed) {
-                const uint64_t hxy = (uint64_t)(uint32_t)cx ^ ((uint64_t)(uint32_t)cy * HASH_P1);
-                r0 = grid_hash_mod(hxy ^ ((uint64_t)(uint32_t)c0z * HASH_P2), g);
-                r1 = grid_hash_mod(hxy ^ ((uint64_t)(uint32_t)c1z * HASH_P2), g);
-            } else {
-                const unsigned rb = ((unsigned)cx * (unsigned)L.res + (unsigned)cy) * (unsigned)L.res;
-                r0 = rb + (unsigned)c0z;
-                r1 = rb + (unsigned)c1z;
-            }
-            row[0] = (unsigned)quad_bcast_i<0>((int)r0); row[1] = (unsigned)quad_bcast_i<0>((int)r1);
-            row[2] = (unsigned)quad_bcast_i<1>((int)r0); row[3] = (unsigned)quad_bcast_i<1>((int)r1);
-            row[4] = (unsigned)quad_bcast_i<2>((int)r0); row[5] = (unsigned)quad_bcast_i<2>((int)r1);
-            row[6] = (unsigned)quad_bcast_i<3>((int)r0); row[7] = (unsigned)quad_bcast_i<3>((int)r1);
-        };
+        // the rows and offsets of point j (a binder only: called directly, quad_point_rows compiles this kernel to other code)
+        auto next_rows = [&](int j, unsigned* row, float* tq) { quad_point_rows(g, L, q, rdlane(xi, j), rdlane(yi, j), rdlane(zi, j), row, tq); };
         // Software pipeline (round 6): the 8 row gathers of point j + 1 are in flight while point j is reduced and scattered.  The
         // wave walks its points one after the other, and each point used to be a full dependent round trip — index math, 8 KB of
         // random 64-byte rows out of a 1 GB table, reductions, atomics: ~8 us per point at two waves per SIMD, which is what the
@@ -481,7 +410,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
         unsigned rowc[8];
         float tc[3];
         float4 v[8];
-        prep(0, rowc, tc);
+        next_rows(0, rowc, tc);
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = L.tab[(size_t)rowc[k] * 4];
         for (int j = 0; j < m; ++j) {
@@ -490,7 +419,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
             float4 vn[8];
             const bool more = j + 1 < m;                  // (wave-uniform)
             if (more) {
-                prep(j + 1, rown, tn);
+                next_rows(j + 1, rown, tn);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) vn[k] = L.tab[(size_t)rown[k] * 4];
             }
@@ -507,7 +436,7 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
                 gty += ((k & 2) ? 1.0f : -1.0f) * wx * wz * S;
                 gtz += ((k & 1) ? 1.0f : -1.0f) * wx * wy * S;
                 if (q == 0) {
-                    const float val = (wx * wy * wz) * gl;
+                    const float val = trilinear_weight(k, tx, ux, ty, uy, tz, uz) * gl;
                     if (row[k] == prow[k]) pval[k] += val;
                     else {
                         if (prow[k] != 0xFFFFFFFFu) flush(prow[k], pval[k]);
@@ -534,9 +463,9 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
         }
         __builtin_amdgcn_wave_barrier();              // sgx / sgo are private to the wave: lane 0's stores above before the loads below
         if (io.g_xyz && lane < m) {
-            io.g_xyz[(base + lane) * io.gx_ps + 0 * io.gx_cs] = (sgx[wv][lane][0] + sgo[wv][lane][0]) / ex;
-            io.g_xyz[(base + lane) * io.gx_ps + 1 * io.gx_cs] = (sgx[wv][lane][1] + sgo[wv][lane][1]) / ey;
-            io.g_xyz[(base + lane) * io.gx_ps + 2 * io.gx_cs] = (sgx[wv][lane][2] + sgo[wv][lane][2]) / ez;
+            io.g_xyz[(base + lane) * io.gx_ps + 0 * io.gx_cs] = (sgx[wv][lane][0] + sgo[wv][lane][0]) / box.e[0];
+            io.g_xyz[(base + lane) * io.gx_ps + 1 * io.gx_cs] = (sgx[wv][lane][1] + sgo[wv][lane][1]) / box.e[1];
+            io.g_xyz[(base + lane) * io.gx_ps + 2 * io.gx_cs] = (sgx[wv][lane][2] + sgo[wv][lane][2]) / box.e[2];
         }
         __builtin_amdgcn_wave_barrier();              // ... and those loads before the next tile's stores
     }
@@ -547,10 +476,12 @@ __global__ __launch_bounds__(ENC_BLOCK) void k_part_encode_bwd(GridDev g, EncBwd
         if (key == 0xFFFFFFFFu) continue;
         const int l = (int)(key >> 24);
         const unsigned r = key & 0xFFFFFFu;
+        // (a dense level of a separate_dense grid: grid_level_rs_off / grid_level_table<16> reduce to dense_off[l]; restated, as above)
         float* base = io.rowgrad ? io.rowgrad + g.dense_off[l] : io.g_dense + g.dense_off[l] * 16;
         unsafeAtomicAdd(base + (size_t)r * gstride, cval[j]);
     }
-    // flush the small-level accumulators (dense levels are contiguous in g_dense from dense_off[l])
+    // flush the small-level accumulators (dense levels are contiguous in g_dense from dense_off[l]).  The walk of the small levels above,
+    // restated: as one function, lambda or shared predicate it changes this kernel's code (profiles/grid_level_rules.md)
     int off = 0;
     for (int l = 0; l < 16; ++l) {
         const int64_t rows = (int64_t)g.res[l] * g.res[l] * g.res[l];
@@ -587,12 +518,42 @@ int launch_part_encode_bwd(const GridDev& g, const float* xyz, const float* gout
 // training pipeline: SoA pair lists (stride `stride`), device count, compact row-scalar gradient
 int launch_part_encode_bwd_lists(const GridDev& g, const float* x_soa, const float* gout_soa, float* gx_soa, int64_t stride,
                                  int64_t n_max, const int32_t* count, float* rowgrad, hipStream_t st) {
-    if (g.L != 16 || g.F != 16 || !g.sum || !g.sum_over_features || !g.include_input) {
-        invr_set_error("part encoder backward supports n_levels=16, n_features_per_level=16, sum, sum_over_features, include_input");
-        return 1;
-    }
+    if (!part_grid_supported(g, "part encoder backward", true, false)) return 1;
     EncBwdIO io{x_soa, 1, stride, gout_soa, 1, stride, gx_soa, 1, stride, n_max, count, nullptr, nullptr, rowgrad};
     return launch_part_encode_bwd_io(g, io, st);
+}
+
+int launch_grid_encode_bwd_generic(const GridDev& g, const float* xyz, const float* gout, int64_t n, float* g_dense,
+                                   float* g_hash, float* g_xyz, hipStream_t st, const int32_t* count) {
+    if (n == 0) return 0;
+    const bool fast = part_grid_supported(g, nullptr, true, false) && !count;
+    if (fast) { if (launch_part_encode_bwd(g, xyz, gout, n, g_dense, g_hash, g_xyz, st)) return 1; }
+    else {
+        static bool attr_set = false;
+        const size_t lds = (size_t)BWD_LDS_FLOATS * sizeof(float);
+        if (!attr_set) {
+            if (hipFuncSetAttribute((const void*)k_grid_encode_bwd_rt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+                invr_set_error("hipFuncSetAttribute(k_grid_encode_bwd_rt) failed");
+                return 1;
+            }
+            attr_set = true;
+        }
+        int64_t nb = cdiv(n, BWD_BLOCK);
+        hipLaunchKernelGGL(k_grid_encode_bwd_rt, dim3((unsigned)(nb < 256 ? nb : 256)), dim3(BWD_BLOCK), lds, st, g, xyz, gout, n, count, grid_out_dim(g),
+                           g_dense, g_hash, g_xyz);
+    }
+    INVR_LAUNCH_CHECK();
+    if (g.sum && g.sum_over_features && g.F > 1) {
+        int64_t drows, hrows;
+        grid_table_rows(g, drows, hrows);
+        hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)cdiv(hrows, 256)), dim3(256), 0, st, g_hash, hrows, g.F);
+        INVR_LAUNCH_CHECK();
+        if (g.separate_dense) {
+            hipLaunchKernelGGL(k_expand_rows, dim3((unsigned)cdiv(drows, 256)), dim3(256), 0, st, g_dense, drows, g.F);
+            INVR_LAUNCH_CHECK();
+        }
+    }
+    return 0;
 }
 
 // ---- inference-only row-sum variant -------------------------------------------------------------------
@@ -609,17 +570,6 @@ int launch_part_encode_bwd_lists(const GridDev& g, const float* x_soa, const flo
 //  - div_exact's range test hoisted to once per tile (k_part_encode_rs_xcd): encoder stage 0.538 -> 0.528 ms (r5i)
 // (Measured and not kept, round 5: both levels' gathers + the next tile's coordinates in flight at once — a prepare / fetch / finish
 //  split of the level — 93 instead of 69 VGPRs, 5 instead of 7 waves per SIMD: 0.540 -> 0.588 ms, gpurun_out/r5k.)
-// one level of one point through the row-sum table (wave-uniform level l)
-// FASTDIV: the caller has established, once per tile of pairs, that every lane's three coordinates are in div_exact's proven range
-// and that this level's reciprocal is usable (rcell != 0) — the three quotients then take the 5-instruction reciprocal form without
-// div_exact's per-call range test + ballot + branch (nine wave-uniform branches per level pair of a tile otherwise).  Same bits.
-__device__ __forceinline__ void level_corners_fast(float x, float cell, float rcell, int res, int& c0, int& c1, float& t) {
-    const float f = div_by_rcp(x, cell, rcell);
-    const int a = (int)f, b = (int)(f + 1.0f);
-    c0 = min(max(a, 0), res - 1);
-    c1 = min(max(b, 0), res - 1);
-    t = f - (float)c0;
-}
 // Round 6: the coarse dense level of a workgroup's level pair in LDS (k_part_encode_rs_xcd).  A workgroup of the XCD kernel serves ONE
 // level pair {lg, 15 - lg} of one part at a time; when level lg is dense and small — levels 0..6 of the base-2 parts (8 .. 2197 rows)
 // and level 0 of the body (4096 rows) — its row-sum table is staged once per part into ENC_LDS_ROWS floats of LDS and its 4 pair
@@ -646,7 +596,7 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
     unsigned row[8];
     const float* tab;
     if (l >= g.start_hash) {
-        tab = rs + g.dense_rows + (int64_t)(l - hstart) * g.T;
+        tab = rs + g.dense_rows + (int64_t)(l - hstart) * g.T;          // = rs + grid_level_rs_off(g, l), restated: the shared form changes this kernel
         // (cx * 1) ^ (cy * P1) ^ (cz * P2) in 64 bits (:132-136).  The second corner of an axis is the first + d, d in {0, 1, 2}
         // (0: both clipped to the same cell; 2: f within half an ulp below an integer, where f + 1.0f rounds up and
         // trunc(f + 1) = trunc(f) + 2 — the reference's float arithmetic, :116): its product is the first's + d * prime — one
@@ -662,7 +612,7 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
             // back into [0, T) (T > 2^14 > 2 |delta|: host-checked, GridDev.xdelta), instead of four
             // more 3-round reductions
             const uint32_t m = (uint32_t)c0x ^ (uint32_t)c1x;
-            if (g.mod1r) {
+            if (g.mod1r) {              // (the loop twice, once per reducer: as one template over the reducer it changes this kernel)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const uint64_t X = hx[0] ^ hy[(k >> 1) & 1] ^ hz[k & 1];
@@ -694,7 +644,7 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
             for (int k = 0; k < 8; ++k) row[k] = grid_hash_mod(hx[k >> 2] ^ hy[(k >> 1) & 1] ^ hz[k & 1], g);
         }
     } else {
-        tab = g.separate_dense ? rs + g.dense_off[l] : rs + (int64_t)l * g.T;
+        tab = g.separate_dense ? rs + g.dense_off[l] : rs + (int64_t)l * g.T;      // = rs + grid_level_rs_off(g, l), restated likewise
         // cx*res^2 + cy*res + cz (:124-129) with 24-bit multiplies: a dense level has res^3 <= T < 2^31, so res < 1291 and
         // cx*res + cy < res^2 < 2^21
         const unsigned ures = (unsigned)res;
@@ -732,8 +682,8 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
         const float ux = 1.0f - tx, uy = 1.0f - ty, uz = 1.0f - tz;
         float acc = 0.0f;
 #pragma unroll
-        for (int k = 0; k < 8; ++k)     // weight_k = prod_axis ((1-o) + (2o-1) t)  (:157-158)
-            acc = fmaf(((k & 4) ? tx : ux) * ((k & 2) ? ty : uy) * ((k & 1) ? tz : uz), vv[k], acc);
+        for (int k = 0; k < 8; ++k)     // (the tail below, restated: shared as a function it changes this kernel)
+            acc = fmaf(trilinear_weight(k, tx, ux, ty, uy, tz, uz), vv[k], acc);
         return acc;
     }
     float v[8];
@@ -770,18 +720,17 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
     const float ux = 1.0f - tx, uy = 1.0f - ty, uz = 1.0f - tz;
     float acc = 0.0f;
 #pragma unroll
-    for (int k = 0; k < 8; ++k)     // weight_k = prod_axis ((1-o) + (2o-1) t)  (:157-158)
-        acc = fmaf(((k & 4) ? tx : ux) * ((k & 2) ? ty : uy) * ((k & 1) ? tz : uz), v[k], acc);
+    for (int k = 0; k < 8; ++k)
+        acc = fmaf(trilinear_weight(k, tx, ux, ty, uy, tz, uz), v[k], acc);
     return acc;
 }
 
 __device__ __forceinline__ void encode_rs_part(const GridDev& g, const float* __restrict__ rs, const float* __restrict__ xs,
                                                int64_t stride, int cnt, int64_t cap, float* __restrict__ emb) {
-    const float b0x = g.bounds[0], b0y = g.bounds[1], b0z = g.bounds[2];
-    const float ex = g.bounds[3] - b0x, ey = g.bounds[4] - b0y, ez = g.bounds[5] - b0z;
+    const GridBox box = grid_box(g);
     const int hstart = g.separate_dense ? g.start_hash : 0;
     for (int64_t i = (int64_t)blockIdx.x * RS_BLOCK + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * RS_BLOCK) {
-        const float x = (xs[i] - b0x) / ex, y = (xs[stride + i] - b0y) / ey, z = (xs[2 * stride + i] - b0z) / ez;   // :112
+        const float x = grid_norm(box, 0, xs[i]), y = grid_norm(box, 1, xs[stride + i]), z = grid_norm(box, 2, xs[2 * stride + i]);
         emb[i] = x; emb[cap + i] = y; emb[2 * cap + i] = z;
         emb[(int64_t)(EMB_K - 1) * cap + i] = 0.0f;                 // pad column
 #pragma unroll 2
@@ -817,27 +766,27 @@ __global__ __launch_bounds__(RS_BLOCK) void k_part_encode_rs_xcd(EncodeAllArgs a
         off = (int)((off + (cnt + RS_BLOCK - 1) / RS_BLOCK) % tstride);
         const int lg = (xcd + 3 * p) & 7;
         const int la = lg, lb = 15 - lg;
-        const float b0x = g.bounds[0], b0y = g.bounds[1], b0z = g.bounds[2];
-        const float ex = g.bounds[3] - b0x, ey = g.bounds[4] - b0y, ez = g.bounds[5] - b0z;
+        const GridBox box = grid_box(g);
         const int hstart = g.separate_dense ? g.start_hash : 0;
         // level la in LDS when it is a dense level of at most ENC_LDS_ROWS rows (wave-uniform; res^3 rows, (:124-129))
         const int res_a = g.res[la];
-        const bool lds_a = la < g.start_hash && (int64_t)res_a * res_a * res_a <= ENC_LDS_ROWS && tile0 * RS_BLOCK < cnt;
+        const bool lds_a = la < g.start_hash && grid_level_rows(g, la) <= ENC_LDS_ROWS && tile0 * RS_BLOCK < cnt;
         __syncthreads();                 // (the previous part's look-ups are done before its table is replaced)
         if (lds_a) {
-            const float* __restrict__ src = g.separate_dense ? rs + g.dense_off[la] : rs + (int64_t)la * g.T;
+            const float* __restrict__ src = rs + grid_level_rs_off(g, la, false);
             const int rows = res_a * res_a * res_a;
             for (int t = threadIdx.x; t < rows; t += RS_BLOCK) g_enc_tab[t] = src[t];
             if (threadIdx.x < 2) g_enc_tab[rows + threadIdx.x] = 0.0f;          // (the pair read of the last row's z0 = res - 2 ends at rows - 1: never read, kept defined)
         }
         __syncthreads();
         for (int64_t i = tile0 * RS_BLOCK + threadIdx.x; i < cnt; i += (int64_t)tstride * RS_BLOCK) {
-            const float x = (xs[i] - b0x) / ex, y = (xs[a.stride + i] - b0y) / ey, z = (xs[2 * a.stride + i] - b0z) / ez;   // :112
+            const float x = grid_norm(box, 0, xs[i]), y = grid_norm(box, 1, xs[a.stride + i]), z = grid_norm(box, 2, xs[2 * a.stride + i]);
             if (lg < 3) emb[(int64_t)lg * a.cap + i] = lg == 0 ? x : (lg == 1 ? y : z);
             else if (lg == 3) emb[(int64_t)(EMB_K - 1) * a.cap + i] = 0.0f;          // pad column
             // div_exact's range test, once per tile instead of once per quotient (the coordinates are the same for every level)
             const bool okp = fabsf(x) > 8.7e-19f && fabsf(x) < 1.0e6f && fabsf(y) > 8.7e-19f && fabsf(y) < 1.0e6f && fabsf(z) > 8.7e-19f && fabsf(z) < 1.0e6f;
             const bool fast = __ballot(!okp) == 0ull;
+            // the <FASTDIV, LDSTAB> choice, spelled out per level (as a dispatcher function or lambda it changes this kernel)
             if (lds_a) {
                 if (fast && g.rcell[la] != 0.0f) emb[(int64_t)(3 + la) * a.cap + i] = level_rowsum<true, true>(g, rs, hstart, la, x, y, z);
                 else emb[(int64_t)(3 + la) * a.cap + i] = level_rowsum<false, true>(g, rs, hstart, la, x, y, z);
@@ -875,21 +824,15 @@ int launch_row_sums(const GridDev& g, float* out, hipStream_t st) {
         INVR_LAUNCH_CHECK();
         return 0;
     };
-    if (g.separate_dense) {
-        if (run(g.dense, g.dense_rows, out)) return 1;
-        return run(g.hash, (int64_t)(g.L - g.start_hash) * g.T, out + g.dense_rows);
-    }
-    return run(g.hash, (int64_t)g.L * g.T, out);
+    int64_t drows, hrows;
+    grid_table_rows(g, drows, hrows);
+    if (run(g.dense, drows, out)) return 1;                          // (no rows without separate_dense)
+    return run(g.hash, hrows, out + drows);
 }
 
 int launch_part_encode_rows_all(const EncodeAllArgs& a, hipStream_t st) {
-    for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-        const GridDev& g = a.g[p];
-        if (g.L != 16 || g.F != 16 || !g.sum || !g.sum_over_features || !g.include_input) {
-            invr_set_error("part encoder kernel supports n_levels=16, n_features_per_level=16, sum, sum_over_features, include_input (got L=%d F=%d)", g.L, g.F);
-            return 1;
-        }
-    }
+    for (int p = 0; p < INVR_NUM_PARTS; ++p)
+        if (!part_grid_supported(a.g[p], "part encoder kernel", true, false)) return 1;
     int64_t tiles = cdiv(a.cap, 64 * ENC_WAVES);
     unsigned grid = (unsigned)(tiles < 256 * 4 ? (tiles > 0 ? tiles : 1) : 256 * 4);
     hipLaunchKernelGGL(k_part_encode_rows_all, dim3(grid, INVR_NUM_PARTS), dim3(ENC_BLOCK), 0, st, a);
@@ -898,13 +841,8 @@ int launch_part_encode_rows_all(const EncodeAllArgs& a, hipStream_t st) {
 }
 
 int launch_part_encode_all(const EncodeAllArgs& a, hipStream_t st) {
-    for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-        const GridDev& g = a.g[p];
-        if (g.L != 16 || !g.sum || !g.sum_over_features || !g.include_input || !g.row_sums) {
-            invr_set_error("merged part encoder needs 16-level sum/sum_over_features grids with row-sum tables");
-            return 1;
-        }
-    }
+    for (int p = 0; p < INVR_NUM_PARTS; ++p)
+        if (!part_grid_supported(a.g[p], "merged part encoder", false, true)) return 1;
     int64_t tiles = cdiv(a.cap, RS_BLOCK);
     unsigned gx = (unsigned)(tiles * 8 < 256 * 8 ? (tiles > 0 ? tiles * 8 : 8) : 256 * 8);      // a multiple of 8
     hipLaunchKernelGGL(k_part_encode_rs_xcd, dim3(gx), dim3(RS_BLOCK), 0, st, a);
@@ -914,10 +852,7 @@ int launch_part_encode_all(const EncodeAllArgs& a, hipStream_t st) {
 
 int launch_part_encode(const GridDev& g, const float* x_soa, int64_t stride, const int32_t* count, int64_t cap,
                        float* emb, hipStream_t st) {
-    if (g.L != 16 || g.F != 16 || !g.sum || !g.sum_over_features || !g.include_input) {
-        invr_set_error("part encoder kernel supports n_levels=16, n_features_per_level=16, sum, sum_over_features, include_input (got L=%d F=%d)", g.L, g.F);
-        return 1;
-    }
+    if (!part_grid_supported(g, "part encoder kernel", true, false)) return 1;
     int64_t tiles = cdiv(cap, 64 * ENC_WAVES);
     unsigned grid = (unsigned)(tiles < 256 * 8 ? (tiles > 0 ? tiles : 1) : 256 * 8);
     if (g.row_sums) {

@@ -177,26 +177,14 @@ __device__ __forceinline__ void lane_level_f2(const GridDev& dg, const LaneLevel
     level_corners(x, L.cell, L.res, c0x, c1x, tx);
     level_corners(y, L.cell, L.res, c0y, c1y, ty);
     level_corners(z, L.cell, L.res, c0z, c1z, tz);
-    float2 v[8];
-    if (L.hashed) {
-        const uint64_t hx[2] = {(uint64_t)(uint32_t)c0x, (uint64_t)(uint32_t)c1x};
-        const uint64_t hy[2] = {(uint64_t)(uint32_t)c0y * HASH_P1, (uint64_t)(uint32_t)c1y * HASH_P1};
-        const uint64_t hz[2] = {(uint64_t)(uint32_t)c0z * HASH_P2, (uint64_t)(uint32_t)c1z * HASH_P2};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = L.tab[grid_hash_mod(hx[k >> 2] ^ hy[(k >> 1) & 1] ^ hz[k & 1], dg)];
-    } else {
-        const unsigned ures = (unsigned)L.res;
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            v[k] = L.tab[((unsigned)((k & 4) ? c1x : c0x) * ures + (unsigned)((k & 2) ? c1y : c0y)) * ures + (unsigned)((k & 1) ? c1z : c0z)];
-    }
     const float ux = 1.0f - tx, uy = 1.0f - ty, uz = 1.0f - tz;
     f0 = 0.0f; f1 = 0.0f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const float wk = ((k & 4) ? tx : ux) * ((k & 2) ? ty : uy) * ((k & 1) ? tz : uz);
-        f0 = fmaf(wk, v[k].x, f0);
-        f1 = fmaf(wk, v[k].y, f1);
+        const float2 v = L.tab[grid_row(dg, L.hashed, L.res, (k & 4) ? c1x : c0x, (k & 2) ? c1y : c0y, (k & 1) ? c1z : c0z)];
+        const float wk = trilinear_weight(k, tx, ux, ty, uy, tz, uz);
+        f0 = fmaf(wk, v.x, f0);
+        f1 = fmaf(wk, v.y, f1);
     }
 }
 
@@ -271,13 +259,12 @@ __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(SLICE 
             t.hashed = l >= dg.start_hash;
             t.res = dg.res[l];
             t.cell = dg.cell[l];
-            const float* tb = dg.separate_dense ? (t.hashed ? dg.hash + (int64_t)(l - dg.start_hash) * dg.T * 2 : dg.dense + dg.dense_off[l] * 2)
-                                                : dg.hash + (int64_t)l * dg.T * 2;
-            t.tab = reinterpret_cast<const float2*>(tb);
+            t.tab = reinterpret_cast<const float2*>(grid_level_table<2>(dg, l, t.hashed));
         }
         if (l == 2 * g) LA = t;
         if (l == 2 * g + 1) LB = t;
     }
+    // (grid_box / grid_norm of grid_level.h, restated: through the shared form the slice kernel's prologue comes out reordered)
     const float gb0 = dg.bounds[0], gb1 = dg.bounds[1], gb2 = dg.bounds[2];
     const float ge0 = dg.bounds[3] - gb0, ge1 = dg.bounds[4] - gb1, ge2 = dg.bounds[5] - gb2;
     const float tn = (a.scene.frame_dim[0] - gb2) / ge2;                 // uvt[2] = frame_dim, normalised (:112)
@@ -392,11 +379,10 @@ __global__ __launch_bounds__(DSB_BLOCK) void k_deform_slice_bwd(GridDev dg, DfSl
     const int total = si.off[dg.L];
     for (int e = threadIdx.x; e < total; e += DSB_BLOCK) gS[e] = make_float2(0.f, 0.f);
     __syncthreads();
-    const float gb0 = dg.bounds[0], gb1 = dg.bounds[1];
-    const float ge0 = dg.bounds[3] - gb0, ge1 = dg.bounds[4] - gb1;
+    const GridBox box = grid_box(dg);
     const int off = dg.include_input ? 3 : 0;
     for (int64_t i = (int64_t)blockIdx.x * DSB_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * DSB_BLOCK) {
-        const float un = (uvt[i * 3] - gb0) / ge0, vn = (uvt[i * 3 + 1] - gb1) / ge1;          // :112
+        const float un = grid_norm(box, 0, uvt[i * 3]), vn = grid_norm(box, 1, uvt[i * 3 + 1]);
         const float* go = gfeat + i * feat_dim + off;
 #pragma unroll 2
         for (int l = 0; l < 8; ++l) {
@@ -417,7 +403,7 @@ __global__ __launch_bounds__(DSB_BLOCK) void k_deform_slice_bwd(GridDev dg, DfSl
         }
     }
     __syncthreads();
-    const float tn = (frame_dim[0] - dg.bounds[2]) / (dg.bounds[5] - dg.bounds[2]);
+    const float tn = grid_norm(dg, 2, frame_dim[0]);
     for (int e = threadIdx.x; e < total; e += DSB_BLOCK) {
         const float2 g = gS[e];
         if (g.x == 0.0f && g.y == 0.0f) continue;
@@ -429,17 +415,11 @@ __global__ __launch_bounds__(DSB_BLOCK) void k_deform_slice_bwd(GridDev dg, DfSl
         level_corners(tn, dg.cell[l], res, c0z, c1z, tz);
         const int idx = e - si.off[l], cx = idx / res, cy = idx - cx * res;
         const bool hashed = l >= dg.start_hash;
+        // (grid_level_table<2>'s rule on the gradient tables, restated: through grid_level_like the flush reads the table pointers too)
         float* tb = dg.separate_dense ? (hashed ? g_hash + (int64_t)(l - dg.start_hash) * dg.T * 2 : g_dense + dg.dense_off[l] * 2)
                                       : g_hash + (int64_t)l * dg.T * 2;
-        unsigned r0, r1;
-        if (hashed) {
-            const uint64_t hxy = (uint64_t)(uint32_t)cx ^ ((uint64_t)(uint32_t)cy * HASH_P1);
-            r0 = grid_hash_mod(hxy ^ ((uint64_t)(uint32_t)c0z * HASH_P2), dg);
-            r1 = grid_hash_mod(hxy ^ ((uint64_t)(uint32_t)c1z * HASH_P2), dg);
-        } else {
-            r0 = ((unsigned)cx * (unsigned)res + (unsigned)cy) * (unsigned)res + (unsigned)c0z;
-            r1 = ((unsigned)cx * (unsigned)res + (unsigned)cy) * (unsigned)res + (unsigned)c1z;
-        }
+        const GridRowPair r = grid_row_zpair(dg, hashed, res, c0z, c1z, cx, cy);
+        const unsigned r0 = r.r0, r1 = r.r1;
         const float uz = 1.0f - tz;
         unsafeAtomicAdd(tb + (int64_t)r0 * 2, uz * g.x); unsafeAtomicAdd(tb + (int64_t)r0 * 2 + 1, uz * g.y);
         unsafeAtomicAdd(tb + (int64_t)r1 * 2, tz * g.x); unsafeAtomicAdd(tb + (int64_t)r1 * 2 + 1, tz * g.y);

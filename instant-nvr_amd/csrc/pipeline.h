@@ -179,6 +179,9 @@ struct PartMlpDev {
 // The one shape rule of every part-MLP kernel, forward and backward (they stage weights through the same stage_weights<NRGB>,
 // mlp_common.h, which reads a 64 x 64 middle layer of a three-linear colour MLP); sets the error text when it fails
 bool part_mlp_supported(const PartMlpDev& pm);
+// The one shape rule of the wave-cooperative part-grid kernels (k_encode.hip): 16 levels, sum over features, the input in front;
+// need_F16: 16-float rows; need_row_sums: a row-sum table.  `what` names the caller in the error text (null: no error text)
+bool part_grid_supported(const GridDev& g, const char* what, bool need_F16, bool need_row_sums);
 int launch_part_mlp(const PartMlpDev& pm, const float* emb, const float* d_soa, int64_t stride,
                     const int32_t* count, int64_t cap, float4* raw_direct, hipStream_t st);
 struct MlpBwdOut {                 // k_mlp_bwd.hip; mirrors InvrMlpBwdOut
