@@ -52,6 +52,10 @@ typedef struct InvrGrid {
     int32_t sum;                   /* :163                                                         */
     int32_t sum_over_features;     /* :164                                                         */
     int32_t include_input;         /* :172                                                         */
+    int32_t vertex_rows;           /* 0 = off (where older callers left padding).  > 0, only beside row_sums: row_sums is FOLLOWED,
+                                      from float invr_grid_row_sums_len on, by the de-hashed vertex tables that
+                                      invr_grid_vertex_sums (include/invr_vertex.h) built with max_rows = vertex_rows; the row-sum
+                                      encoder kernels read the levels that have one through it.  At most 2^24.      */
     const float* row_sums;         /* dev, optional (NULL = off): inference-only derived table built by
                                       invr_grid_row_sums — one float per table row = sum of its F features.
                                       Only read by the render path for sum && sum_over_features grids,

@@ -26,7 +26,7 @@ class InvrGrid(C.Structure):
                 ('res', C.c_int32 * MAX_LEVELS), ('cell', C.c_float * MAX_LEVELS),
                 ('dense_off', C.c_int64 * MAX_LEVELS),
                 ('sum', C.c_int32), ('sum_over_features', C.c_int32), ('include_input', C.c_int32),
-                ('row_sums', C.c_void_p)]
+                ('vertex_rows', C.c_int32), ('row_sums', C.c_void_p)]
 
 
 class InvrMlpBwdOut(C.Structure):
@@ -211,7 +211,17 @@ def _signatures_sample():
     }
 
 
+def _signatures_vertex():
+    """The same table for include/invr_vertex.h (tests/test_abi_vertex_sums_cpu.py holds it against that header's text)."""
+    i64, vp = C.c_int64, C.c_void_p
+    return {
+        'invr_grid_vertex_sums_len': (i64, [vp, i64]),
+        'invr_grid_vertex_sums': (C.c_int, [vp, i64, vp, vp]),
+    }
+
+
 SIGNATURES = _signatures()
+SIGNATURES_VERTEX = _signatures_vertex()
 SIGNATURES_PERCEPTUAL = _signatures_perceptual()
 SIGNATURES_MESH = _signatures_mesh()
 SIGNATURES_BATCH = _signatures_batch()
@@ -234,7 +244,7 @@ def lib():
                                'There is no CPU fallback for the render path.' % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_MESH.items())
-                                          + list(SIGNATURES_BATCH.items()) + list(SIGNATURES_SAMPLE.items())):
+                                          + list(SIGNATURES_BATCH.items()) + list(SIGNATURES_SAMPLE.items()) + list(SIGNATURES_VERTEX.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
         if L.invr_version() != ABI_VERSION:

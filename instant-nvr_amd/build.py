@@ -14,7 +14,7 @@ INCLUDE = os.path.join(HERE, '..', 'include')
 def headers():
     """Every header a source may include: an edit to any of them rebuilds every object."""
     return ([os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith('.h')]
-            + [os.path.join(INCLUDE, h) for h in ('invr.h', 'invr_perceptual.h', 'invr_mesh.h', 'invr_batch.h', 'invr_sample.h')])
+            + [os.path.join(INCLUDE, h) for h in ('invr.h', 'invr_perceptual.h', 'invr_mesh.h', 'invr_batch.h', 'invr_sample.h', 'invr_vertex.h')])
 
 
 # -ffp-contract=off: FMAs only where the source says fmaf(), so the discrete decisions of the path

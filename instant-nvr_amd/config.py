@@ -83,6 +83,10 @@ DEFAULTS = {
     'train_hip_mlp': True,   # training: part MLPs forward + backward on the HIP kernels (False: torch ops, autograd.part_field)
     'voxel_size': [0.005, 0.005, 0.005],   # lib/config/config.py:88: the grid step of the mesh extraction (invr.mesh)
     'eval_row_sums': True,   # eval-mode renders read the part grids through derived row-sum tables (invr_grid_row_sums)
+    # ... and every hashed level of at most this many vertices through a de-hashed vertex table (invr_grid_vertex_sums; <= 2^24, 0 = off).
+    # 2^24 had the lowest frame time of 2^20 / 2^22 / 2^24 on the bench frame, for 453 MB of derived tables; 2^22 keeps three quarters
+    # of the gain in 71 MB (profiles/vertex_tables.md)
+    'eval_vertex_rows': 1 << 24,
     # image loss: configs/inb/inb_377.yaml sets use_lpips True (VGG19 from torchvision, absent on this image).  The stand-alone
     # default is the plain MSE; adopt() takes the host's value and NetworkWrapper raises if no perceptual loss can be had.
     'use_lpips': False, 'use_ssim': False, 'use_fourier': False, 'use_tv_image': False, 'vgg19_weights': None,

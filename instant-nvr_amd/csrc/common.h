@@ -65,6 +65,11 @@ struct GridDev {
     int32_t sum, sum_over_features, include_input;
     const float* row_sums;      // optional inference-only (rows,) table of per-row feature sums
     int64_t dense_rows;         // rows of `dense` (0 when !separate_dense)
+    // optional, with row_sums (InvrGrid.vertex_rows; filled by make_grid_dev): hashed levels of few vertices de-hashed into dense
+    // (res^3,) tables, back to back behind the row sums (k_encode.hip: k_vertex_sums); vertex_off[l] = first float of level l's
+    // table, -1 = the level keeps its hashed route
+    const float* vertex_sums;
+    int64_t vertex_off[INVR_MAX_LEVELS];
 };
 
 struct VolDev {          // (Dx,Dy,Dz,C) volume + (2,3) bounds
@@ -376,6 +381,7 @@ int launch_adam_advance(void* tensors, int n, double b1, double b2, hipStream_t 
 int launch_adam(const void* tensors, const int32_t* chunk_tensor, const int32_t* chunk_index, int64_t n_chunks, double b1, double b2,
                 float eps, hipStream_t st);
 int launch_row_sums(const GridDev& g, float* out, hipStream_t st);
+int launch_vertex_sums(const GridDev& g, int64_t max_rows, float* out, hipStream_t st);
 int launch_rigid_transformation(const double* poses, const double* joints, const int32_t* parents, float* A, hipStream_t st);
 int launch_pack_parts(const float* ppts, const float* weights, const int64_t* parts, const float* tpose, int n_verts, int n_w,
                       int stride, float overlap, float* part_pts, float* part_pbw, int64_t* lengths2, float* bounds, hipStream_t st);

@@ -36,6 +36,21 @@ __host__ __device__ __forceinline__ void grid_table_rows(const GridDev& g, int64
     dense_rows = g.separate_dense ? g.dense_rows : 0;
     hash_rows = (int64_t)(g.separate_dense ? g.L - g.start_hash : g.L) * g.T;
 }
+// De-hashed vertex tables (GridDev.vertex_sums): a hashed level of at most max_rows vertices gets a dense (res^3,) table of the row sums
+// its vertices name; the tables lie back to back in level order, two pad floats behind the last (the dense route of level_rowsum
+// reads 8-byte z pairs).  GRID_VERTEX_MAX_ROWS bounds max_rows: res^3 <= 2^24 gives res <= 256, so every operand of that route's
+// __umul24 (cx, cx res + cy < res^2 <= 2^16, res) is far below 2^24.  -> floats in all (0: no level qualifies); off[l] = -1 elsewhere.
+#define GRID_VERTEX_MAX_ROWS (1ll << 24)          // = include/invr_vertex.h INVR_VERTEX_MAX_ROWS (invr_abi.hip asserts it)
+__host__ __device__ __forceinline__ int64_t grid_vertex_layout(const GridDev& g, int64_t max_rows, int64_t* off) {
+    int64_t total = 0;
+    for (int l = 0; l < INVR_MAX_LEVELS; ++l) {
+        const int64_t rows = (int64_t)g.res[l] * g.res[l] * g.res[l];
+        const bool own = l >= g.start_hash && l < g.L && rows <= max_rows && max_rows <= GRID_VERTEX_MAX_ROWS;
+        off[l] = own ? total : -1;
+        if (own) total += rows;
+    }
+    return total ? total + 2 : 0;
+}
 // floats per encoded point
 __host__ __device__ __forceinline__ int grid_out_dim(const GridDev& g) {
     return (g.sum ? (g.sum_over_features ? g.L : g.F) : g.L * g.F) + (g.include_input ? 3 : 0);

@@ -11,6 +11,8 @@
 #include "pipeline.h"
 #include "grid_level.h"
 #include "train.h"
+#include "../../include/invr_vertex.h"
+static_assert(GRID_VERTEX_MAX_ROWS == INVR_VERTEX_MAX_ROWS, "one limit");
 
 static thread_local char g_err[512] = "";
 
@@ -95,6 +97,13 @@ GridDev make_grid_dev(const InvrGrid* g) {
     d.dense_rows = 0;
     if (g->separate_dense)
         for (int l = 0; l < g->start_hash && l < INVR_MAX_LEVELS; ++l) d.dense_rows += (int64_t)g->res[l] * g->res[l] * g->res[l];
+    // de-hashed vertex tables (InvrGrid.vertex_rows): behind the row sums they were built from, laid out by grid_vertex_layout
+    for (int l = 0; l < INVR_MAX_LEVELS; ++l) d.vertex_off[l] = -1;
+    if (d.row_sums && g->vertex_rows > 0 && g->n_levels >= 1 && g->n_levels <= INVR_MAX_LEVELS) {
+        int64_t drows, hrows;
+        grid_table_rows(d, drows, hrows);
+        if (grid_vertex_layout(d, g->vertex_rows, d.vertex_off) > 0) d.vertex_sums = d.row_sums + drows + hrows;
+    }
     return d;
 }
 
@@ -138,6 +147,7 @@ static int check_grid(const InvrGrid* g, const char* what) {
     INVR_CHECK(!g->separate_dense || g->dense != nullptr, "%s: separate_dense without dense table", what);
     INVR_CHECK(g->table_len > 1 && g->table_len < (1ll << 31), "%s: table_len out of range", what);
     for (int l = 0; l < g->n_levels; ++l) INVR_CHECK(g->res[l] >= 2 && g->res[l] <= 8192, "%s: level %d resolution %d out of range", what, l, g->res[l]);
+    INVR_CHECK(g->vertex_rows >= 0 && g->vertex_rows <= GRID_VERTEX_MAX_ROWS, "%s: vertex_rows %d outside [0, 2^24]", what, g->vertex_rows);
     return 0;
 }
 
@@ -818,6 +828,30 @@ extern "C" int invr_grid_row_sums(const InvrGrid* grid, float* out, void* stream
     INVR_CHECK(grid->sum && grid->sum_over_features, "invr_grid_row_sums: only sum && sum_over_features grids have row sums");
     INVR_CHECK(grid->n_features % 4 == 0, "invr_grid_row_sums: n_features must be a multiple of 4");
     return launch_row_sums(make_grid_dev(grid), out, (hipStream_t)stream);
+}
+
+extern "C" int64_t invr_grid_vertex_sums_len(const InvrGrid* grid, int64_t max_rows) {
+    if (!grid || grid->n_levels < 1 || grid->n_levels > INVR_MAX_LEVELS || max_rows <= 0) return 0;
+    if (max_rows > GRID_VERTEX_MAX_ROWS) {
+        invr_set_error("invr_grid_vertex_sums_len: max_rows %lld above the limit of 2^24 vertices per level", (long long)max_rows);
+        return -1;
+    }
+    int64_t off[INVR_MAX_LEVELS];
+    return grid_vertex_layout(make_grid_dev(grid), max_rows, off);
+}
+
+extern "C" int invr_grid_vertex_sums(const InvrGrid* grid, int64_t max_rows, float* out, void* stream) {
+    INVR_CHECK(grid, "invr_grid_vertex_sums: null pointer");
+    if (check_grid(grid, "grid")) return 1;
+    INVR_CHECK(max_rows >= 0 && max_rows <= GRID_VERTEX_MAX_ROWS, "invr_grid_vertex_sums: max_rows %lld outside [0, 2^24] vertices per level",
+               (long long)max_rows);
+    INVR_CHECK(grid->sum && grid->sum_over_features && grid->row_sums, "invr_grid_vertex_sums: needs grid->row_sums (invr_grid_row_sums)");
+    GridDev g = make_grid_dev(grid);
+    g.vertex_sums = nullptr;          // (the grid's own tables, if it names any, are not read: the builder's source is the row sums)
+    int64_t off[INVR_MAX_LEVELS];
+    if (grid_vertex_layout(g, max_rows, off) == 0) return 0;
+    INVR_CHECK(out, "invr_grid_vertex_sums: null pointer");
+    return launch_vertex_sums(g, max_rows, out, (hipStream_t)stream);
 }
 
 extern "C" int32_t invr_adam_chunk_elems(void) { return 16384; }

@@ -595,7 +595,10 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
     }
     unsigned row[8];
     const float* tab;
-    if (l >= g.start_hash) {
+    // a hashed level whose vertices were de-hashed into a dense (res^3,) table (GridDev.vertex_sums) is an ordinary dense level: the
+    // same eight values in the same corner order (x-major, z fastest, in both branches) — same bits; wave-uniform
+    const bool vtab = l >= g.start_hash && g.vertex_sums && g.vertex_off[l] >= 0;
+    if (l >= g.start_hash && !vtab) {
         tab = rs + g.dense_rows + (int64_t)(l - hstart) * g.T;          // = rs + grid_level_rs_off(g, l), restated: the shared form changes this kernel
         // (cx * 1) ^ (cy * P1) ^ (cz * P2) in 64 bits (:132-136).  The second corner of an axis is the first + d, d in {0, 1, 2}
         // (0: both clipped to the same cell; 2: f within half an ulp below an integer, where f + 1.0f rounds up and
@@ -644,9 +647,10 @@ __device__ __forceinline__ float level_rowsum(const GridDev& g, const float* __r
             for (int k = 0; k < 8; ++k) row[k] = grid_hash_mod(hx[k >> 2] ^ hy[(k >> 1) & 1] ^ hz[k & 1], g);
         }
     } else {
-        tab = g.separate_dense ? rs + g.dense_off[l] : rs + (int64_t)l * g.T;      // = rs + grid_level_rs_off(g, l), restated likewise
+        tab = vtab ? g.vertex_sums + g.vertex_off[l]
+                   : g.separate_dense ? rs + g.dense_off[l] : rs + (int64_t)l * g.T;      // = rs + grid_level_rs_off(g, l), restated likewise
         // cx*res^2 + cy*res + cz (:124-129) with 24-bit multiplies: a dense level has res^3 <= T < 2^31, so res < 1291 and
-        // cx*res + cy < res^2 < 2^21
+        // cx*res + cy < res^2 < 2^21 (a vertex table: res <= 256, GRID_VERTEX_MAX_ROWS)
         const unsigned ures = (unsigned)res;
         const unsigned bx0 = __umul24((unsigned)c0x, ures), bx1 = __umul24((unsigned)c1x, ures);
         const unsigned b00 = __umul24(bx0 + (unsigned)c0y, ures), b01 = __umul24(bx0 + (unsigned)c1y, ures);
@@ -813,6 +817,31 @@ __global__ void k_row_sums(const float* __restrict__ tab, int64_t rows, int F, f
     } else {
         atomicAdd(out + r, s);                                       // F != 16: rare; out pre-zeroed by the launcher
     }
+}
+
+// De-hashed vertex table of ONE hashed level: out[(cx res + cy) res + cz] = the row sum its vertex names, through the grid's own
+// reducer (grid_row).  A constant of the model like the row sums themselves: rebuilt when they are.
+__global__ void k_vertex_sums(GridDev g, const float* __restrict__ rs, int l, int64_t rows, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    const int res = g.res[l];
+    const int cz = (int)(i % res), cy = (int)(i / res % res), cx = (int)(i / ((int64_t)res * res));
+    out[i] = rs[grid_level_rs_off(g, l, true) + grid_row(g, true, res, cx, cy, cz)];
+}
+
+// every level grid_vertex_layout gives a table, back to back, + the two pad floats; g.row_sums is the source
+int launch_vertex_sums(const GridDev& g, int64_t max_rows, float* out, hipStream_t st) {
+    int64_t off[INVR_MAX_LEVELS];
+    const int64_t total = grid_vertex_layout(g, max_rows, off);
+    if (total == 0) return 0;
+    for (int l = 0; l < g.L; ++l) {
+        if (off[l] < 0) continue;
+        const int64_t rows = (int64_t)g.res[l] * g.res[l] * g.res[l];
+        hipLaunchKernelGGL(k_vertex_sums, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, st, g, g.row_sums, l, rows, out + off[l]);
+        INVR_LAUNCH_CHECK();
+    }
+    INVR_HIP(hipMemsetAsync(out + total - 2, 0, 2 * sizeof(float), st));          // (read by no pair load — the last one ends at total - 3 — kept defined)
+    return 0;
 }
 
 int launch_row_sums(const GridDev& g, float* out, hipStream_t st) {

@@ -47,7 +47,7 @@ class Embedder(nn.Module):
 
     def __getstate__(self):
         d = self.__dict__.copy()
-        for k in ('_rs', '_rs_key', '_row_grad', 'row_grad_dirty'):
+        for k in ('_rs', '_rs_key', '_vs', '_vs_key', '_row_grad', 'row_grad_dirty'):
             d.pop(k, None)
         return d
 
@@ -64,6 +64,8 @@ class Embedder(nn.Module):
         tables through a path the tensor version counters do not see (p.data.copy_(), raw-pointer kernels)."""
         self._rs_key = None
         self._rs = None
+        self._vs_key = None          # (the vertex tables are built from the row sums)
+        self._vs = None
 
     def train(self, mode=True):
         # every train <-> eval transition rebuilds the derived table: in-place writes through .data (its own version
@@ -89,6 +91,33 @@ class Embedder(nn.Module):
             _abi.check(_abi.lib().invr_grid_row_sums(C.byref(g), _abi.ptr(rs), _abi.stream_ptr()))
             self._rs, self._rs_key = rs, key
         return self._rs
+
+    def vertex_sums(self, max_rows):
+        """Inference-only row sums FOLLOWED by the de-hashed vertex tables (include/invr_vertex.h) of the hashed levels of at most
+        `max_rows` vertices, as one buffer: what InvrGrid.row_sums points at when InvrGrid.vertex_rows = max_rows.  None when no level
+        qualifies (the plain row_sums() then serve).  Cached under the key of row_sums() and dropped with it: table versions /
+        storage, train()/eval(), load_state_dict, invalidate_row_sums()."""
+        L = _abi.lib()
+        tabs = [self.hash] + ([self.dense] if self.separate_dense else [])
+        key = tuple((t.data_ptr(), t._version, str(t.device)) for t in tabs) + (int(max_rows),)
+        if getattr(self, '_vs_key', None) != key:
+            n_vs = params.vertex_layout(self.spec, max_rows)[1]
+            buf = None
+            if n_vs:
+                keep = []
+                g = self.grid_struct(keep)
+                n_rs = L.invr_grid_row_sums_len(C.byref(g))
+                assert L.invr_grid_vertex_sums_len(C.byref(g), int(max_rows)) == n_vs, (self.partname, n_vs)
+                buf = torch.empty(n_rs + n_vs, device=self.hash.device, dtype=torch.float32)
+                _abi.check(L.invr_grid_row_sums(C.byref(g), _abi.ptr(buf), _abi.stream_ptr()))
+                g.row_sums = buf.data_ptr()
+                _abi.check(L.invr_grid_vertex_sums(C.byref(g), int(max_rows), C.c_void_p(buf.data_ptr() + 4 * n_rs), _abi.stream_ptr()))
+            self._vs, self._vs_key = buf, key
+        return self._vs
+
+    def derived_bytes(self):
+        """Bytes of the inference-only derived tables this grid holds right now (row sums, row sums + vertex tables)."""
+        return sum(t.numel() * t.element_size() for t in (getattr(self, '_rs', None), getattr(self, '_vs', None)) if t is not None)
 
     def row_grad(self):
         """Persistent compact table gradient of a sum-over-features grid (invr_train_bwd): one float per table row in
@@ -244,7 +273,12 @@ class Network(nn.Module):
             for i, pn in enumerate(self.tpose_human.part_networks):
                 e = pn.embedder
                 if e.spec['sum'] and e.spec['sum_over_features'] and e.f % 4 == 0:
-                    rs = e.row_sums()
+                    vrows = int(self.cfg.get('eval_vertex_rows', 0) or 0)
+                    # ... and, behind them in one buffer, their small hashed levels through de-hashed vertex tables
+                    rs = e.vertex_sums(vrows) if vrows > 0 else None
+                    m.part[i].grid.vertex_rows = vrows if rs is not None else 0
+                    if rs is None:
+                        rs = e.row_sums()
                     keep.append(rs)
                     m.part[i].grid.row_sums = rs.data_ptr()
         return m

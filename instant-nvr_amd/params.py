@@ -60,6 +60,23 @@ def grid_spec(n_levels=16, n_features_per_level=16, b=1.38, log2_hashmap_size=18
                 bbox=np.asarray(bbox, dtype=np.float32).reshape(2, 3), out_dim=out_dim)
 
 
+VERTEX_MAX_ROWS = 2 ** 24          # include/invr_vertex.h INVR_VERTEX_MAX_ROWS: more vertices per level are refused
+
+
+def vertex_layout(spec, max_rows):
+    """Layout of the de-hashed vertex tables (include/invr_vertex.h: invr_grid_vertex_sums) -> (first float per level, floats in all): every
+    hashed level of at most `max_rows` vertices gets res^3 floats, back to back in level order, two pad floats behind the last;
+    -1 = the level keeps its hashed route; (all -1, 0) when no level qualifies."""
+    if int(max_rows) > VERTEX_MAX_ROWS:
+        raise ValueError('invr: eval_vertex_rows = %d is above the limit of 2^24 vertices per level' % int(max_rows))
+    off, total = [], 0
+    for l in range(spec['L']):
+        own = l >= spec['start_hash'] and spec['cnt'][l] <= int(max_rows)
+        off.append(total if own else -1)
+        total += spec['cnt'][l] if own else 0
+    return off, (total + 2 if total else 0)
+
+
 def part_grid_spec(cfg, partname):
     pc = cfg.partnet[partname]
     return grid_spec(bbox=pc.bbox, **pc.embedder.kwargs)
