@@ -348,8 +348,8 @@ def mesh_views(ws, dims):
 def perceptual_pack(weights, biases, packed=None):
     """The packed weight image of invr_perceptual_pack_weights from the four (out, in, 3, 3) weights and (out) biases (device tensors)."""
     L = lib()
-    ws = [_f32c(t) for t in weights]
-    bs = [_f32c(t) for t in biases]
+    ws = [f32c(t) for t in weights]
+    bs = [f32c(t) for t in biases]
     assert [tuple(t.shape) for t in ws] == [(64, 3, 3, 3), (64, 64, 3, 3), (128, 64, 3, 3), (128, 128, 3, 3)], [tuple(t.shape) for t in ws]
     assert [tuple(t.shape) for t in bs] == [(64,), (64,), (128,), (128,)]
     if packed is None:
@@ -374,19 +374,20 @@ def ptr(t, dtype=torch.float32):
     return C.c_void_p(t.data_ptr())
 
 
-def _f32c(t):
+def f32c(t):
+    """What ptr() asks for: the detached, fp32, contiguous form of a tensor (itself where it already is that)."""
     return t.detach().to(torch.float32).contiguous()
 
 
 def make_grid(spec, dense, hsh, bounds, keep):
     """InvrGrid from params.grid_spec(...) + table tensors.  `keep` collects tensors to keep alive."""
     g = InvrGrid()
-    hsh = _f32c(hsh); keep.append(hsh)
+    hsh = f32c(hsh); keep.append(hsh)
     g.hash = hsh.data_ptr()
     if dense is not None:
-        dense = _f32c(dense); keep.append(dense)
+        dense = f32c(dense); keep.append(dense)
         g.dense = dense.data_ptr()
-    bounds = _f32c(bounds); keep.append(bounds)
+    bounds = f32c(bounds); keep.append(bounds)
     g.bounds = bounds.data_ptr()
     g.n_levels, g.n_features, g.start_hash = spec['L'], spec['F'], spec['start_hash']
     g.separate_dense, g.table_len = int(spec['separate_dense']), spec['T']
@@ -402,7 +403,7 @@ def make_mlp(weights, biases, keep):
     m = InvrMlp()
     m.n_linear = len(weights)
     for i, (w, b) in enumerate(zip(weights, biases)):
-        w, b = _f32c(w), _f32c(b)
+        w, b = f32c(w), f32c(b)
         keep += [w, b]
         m.weight[i], m.bias[i] = w.data_ptr(), b.data_ptr()
         m.dims[i], m.dims[i + 1] = w.shape[1], w.shape[0]
@@ -427,7 +428,7 @@ def make_model(sd, cfg, keep):
                             [sd[q + 'occ.linears.%d.bias' % k] for k in range(len(occ_dims) - 1)], keep)
         part.rgb = make_mlp([sd[q + 'rgb.linears.%d.weight' % k] for k in range(len(rgb_dims) - 1)],
                             [sd[q + 'rgb.linears.%d.bias' % k] for k in range(len(rgb_dims) - 1)], keep)
-        lat = _f32c(sd[q + 'rgb_latent']); keep.append(lat)
+        lat = f32c(sd[q + 'rgb_latent']); keep.append(lat)
         part.rgb_latent = lat.data_ptr()
         part.latent_dim, part.num_latent_code = lat.shape[1], lat.shape[0]
     m.n_dir_freq = cfg.viewdir_embedder.kwargs['res']
@@ -440,7 +441,7 @@ def make_scene(batch, cfg, keep):
     s = InvrScene()
 
     def f(k):
-        t = _f32c(batch[k][0]); keep.append(t)
+        t = f32c(batch[k][0]); keep.append(t)
         return t
     s.R, s.Th, s.A, s.big_A = f('R').data_ptr(), f('Th').data_ptr(), f('A').data_ptr(), f('big_A').data_ptr()
     pbw, tuv = f('pbw'), f('tuv')

@@ -20,6 +20,8 @@ import torch.nn.functional as F
 
 from . import _abi
 from .config import NUM_PARTS
+from .lazyret import LazyDict
+from .renderer import pair_rows, unlisted_bigpose
 
 
 class GridEncodeFn(torch.autograd.Function):
@@ -29,7 +31,7 @@ class GridEncodeFn(torch.autograd.Function):
     def forward(ctx, xyz, dense, hsh, bounds, spec):
         keep = []
         g = _abi.make_grid(spec, dense, hsh, bounds, keep)
-        x = xyz.detach().to(torch.float32).contiguous()
+        x = _abi.f32c(xyz)
         out = torch.empty(x.shape[0], spec['out_dim'], device=x.device, dtype=torch.float32)
         _abi.check(_abi.lib().invr_grid_encode_fwd(C.byref(g), _abi.ptr(x), x.shape[0], _abi.ptr(out), _abi.stream_ptr()))
         ctx.save_for_backward(x, dense, hsh, bounds)
@@ -56,7 +58,7 @@ class CompositeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, raw):
-        raw = raw.detach().to(torch.float32).contiguous()
+        raw = _abi.f32c(raw)
         R, S = raw.shape[:2]
         w = torch.empty(R, S, device=raw.device)
         rgb = torch.empty(R, 3, device=raw.device)
@@ -81,7 +83,7 @@ def sample_volume(vol, bounds, pts, c0, nc):
     """pts_sample_uv / pts_sample_blend_weights (blend_utils.py:501-555), no gradient."""
     vol = vol.contiguous()
     dims = (C.c_int32 * 3)(*vol.shape[:3])
-    pts = pts.detach().to(torch.float32).contiguous()
+    pts = _abi.f32c(pts)
     out = torch.empty(pts.shape[0], nc, device=pts.device)
     bounds = bounds.contiguous()                       # held in a name: the pointer must outlive the call
     _abi.check(_abi.lib().invr_sample_volume(_abi.ptr(vol), dims, vol.shape[3], c0, nc, _abi.ptr(bounds),
@@ -148,19 +150,6 @@ def deform(net, batch, pts):
     h = F.softplus(linear(dfm.mlp[0], feat))
     h = F.softplus(linear(dfm.mlp[2], h))
     return 0.05 * torch.tanh(linear(dfm.mlp[4], h))
-
-
-def _splitk(gy, x):
-    """gy (n,out), x (n,in) -> gy^T x (out,in) as a slab-batched GEMM (see LinearFn)."""
-    n = x.shape[0]
-    main = (n // _SPLIT_ROWS) * _SPLIT_ROWS
-    gw = None
-    if main:
-        gw = torch.bmm(gy[:main].view(-1, _SPLIT_ROWS, gy.shape[1]).transpose(1, 2), x[:main].view(-1, _SPLIT_ROWS, x.shape[1])).sum(0)
-    if main < n:
-        tail = gy[main:].t() @ x[main:]
-        gw = tail if gw is None else gw + tail
-    return gw
 
 
 def _rgb1_col(s, g):
@@ -327,15 +316,8 @@ def render_train(net, batch, geo, views, stats, n_rays, S, pair_noise, ctx=None,
     resd = resd_flat.view(Na + 1, P, 3)[:Na]
     tpts = tpts_flat.view(Na + 1, P, 3)[:Na]
     if ctx is not None and Na:
-        # rows that are neither listed nor far: init_bigpose under that part's 4-NN weights, as the reference computes it for
-        # all Na x P rows (inb_part_network_multiassign.py:96-120) — see renderer.dense_train_rows
-        from . import stages
-        ro, rd, nr, fa = rays
         with torch.no_grad():
-            pts, pdirs = stages.pose_points(ctx.scene, ro, rd, nr, fa, S, views['active_idx'][:Na], jitter=jitter)
-            bw, _ = stages.knn_blend(ctx.scene, pts)
-            tp, _, _ = stages.warp_deform(ctx.scene, ctx.model, pts, pdirs, bw, torch.zeros(Na, P, dtype=torch.uint8, device=dev))
-            known = (((views['pflags'][:Na].to(torch.int32) | far)[:, None] >> torch.arange(P, device=dev)[None]) & 1).bool()
+            known, tp = unlisted_bigpose(views, Na, far, ctx, rays, S, jitter)
         tpts = torch.where(known[..., None], tpts, tp)
     tocc = raws[..., 3]
     aggr = cfg.get('aggr', '') or ''
@@ -359,16 +341,8 @@ def render_train(net, batch, geo, views, stats, n_rays, S, pair_noise, ctx=None,
     weights, rgb_map, acc_map = CompositeFn.apply(raw_full.view(n_rays, S, 4))
     ret = {'rgb_map': rgb_map[None], 'acc_map': acc_map[None], 'raw': raw_full[None], 'occ': raw_full[None, :, 3:],
            'resd': resd.reshape(1, -1, 3), 'tpts': tpts.reshape(1, -1, 3).detach(), 'tocc': tocc.reshape(1, -1, 1)}
-    if cfg.use_pair_reg:                                                                 # inb_renderer.py:78-94
-        reg = ((tocc.detach().reshape(-1) - 0.5).abs() < 0.02).nonzero(as_tuple=True)[0]
-        if reg.numel():
-            reg_tpts = ret['tpts'].reshape(-1, 3)[reg]
-            reg_resd = resd.reshape(-1, 3)[reg]
-            neighbor = reg_tpts + (pair_noise(reg_tpts[None])[0] - 0.5) * 0.01
-            nei = deform(net, batch, neighbor)
-            ret['oresd'] = torch.cat([reg_resd[None], nei[None]], dim=1)
-        else:
-            ret['oresd'] = torch.zeros(1, 0, 3, device=dev)
+    if cfg.use_pair_reg:
+        ret['oresd'] = pair_rows(tocc, ret['tpts'], resd, lambda reg, like: pair_noise(like), lambda x: deform(net, batch, x[0])[None])
     if cfg.use_reg_distortion:
         ret['reg_distortion_loss'] = distortion(weights, geo['z_vals'])[None]
     return ret
@@ -496,7 +470,7 @@ class TrainRenderFn(torch.autograd.Function):
     def forward(ctx, net, rctx, arena, ray_o, ray_d, near, far, n_samples, jitter, pair_noise, max_active, *params):
         L = _abi.lib()
         dev = ray_o.device
-        f = lambda t: t.detach().to(torch.float32).contiguous()
+        f = _abi.f32c
         ray_o, ray_d, near, far = f(ray_o), f(ray_d), f(near), f(far)
         n, S = ray_o.shape[0], int(n_samples)
         N = n * S
@@ -662,77 +636,25 @@ class TrainLossPerceptualFn(torch.autograd.Function):
         return (g_rgb, None, g_dist, g_terms) + (None,) * 10
 
 
-class LazyTrainRet(dict):
+class LazyTrainRet(LazyDict):
     """The train-mode return dict of Renderer.render.  rgb_map / acc_map / raw / occ / reg_distortion_loss and the fused
     regulariser terms (offset_loss, pair_loss: differentiable scalars) are present; the reference's dynamic-shape tensors
     resd / tpts / tocc / oresd are materialised from the workspace on first access (that read-back synchronises with the
-    device, like the reference's own nonzero()s; they are detached — the gradient flows through the fused terms)."""
+    device, like the reference's own nonzero()s; they are detached — the gradient flows through the fused terms).  Every dict view
+    sees them (lazyret.LazyDict): a host loop `for k, v in dict(ret).items()` finds offset_loss / pair_loss / resd ..."""
     def __init__(self, base, lazy_keys, materialise, thunks=None):
         super().__init__(base)
-        self._lazy, self._mat, self._done = tuple(lazy_keys), materialise, False
+        self._lazy, self._mat = frozenset(lazy_keys), materialise          # ONE materialise() call makes all of `lazy_keys`
         self._thunks = dict(thunks or {})       # cheap derived entries (a few torch ops, no synchronisation), built on first access:
                                                 # the trainer's fused objective never touches them (offset_loss / pair_loss)
 
-    def _thunk(self, k):
-        if k in self._thunks:
-            dict.__setitem__(self, k, self._thunks.pop(k)())
+    def _promised(self):
+        return self._thunks.keys() | self._lazy
 
-    def _fill(self):
-        for k in tuple(self._thunks):
-            self._thunk(k)
-        if not self._done:
-            self._done = True
-            for k, v in self._mat().items():
-                dict.__setitem__(self, k, v)
-
-    def __contains__(self, k):
-        return dict.__contains__(self, k) or k in self._thunks or (not self._done and k in self._lazy)
-
-    def __getitem__(self, k):
-        self._thunk(k)
-        if not dict.__contains__(self, k) and k in self._lazy:
-            self._fill()
-        return dict.__getitem__(self, k)
-
-    def get(self, k, d=None):
-        return self[k] if k in self else d
-
-    def keys(self):
-        self._fill()
-        return dict.keys(self)
-
-    def items(self):
-        self._fill()
-        return dict.items(self)
-
-    # every other dict view fills first too (dict's C fast paths — values(), iteration, len(), dict(ret), copy() — would not see the
-    # thunks / lazy tensors otherwise: a host loop `for k, v in dict(ret).items()` must find offset_loss / pair_loss / resd ...)
-    def values(self):
-        self._fill()
-        return dict.values(self)
-
-    def __iter__(self):
-        self._fill()
-        return dict.__iter__(self)
-
-    def __len__(self):
-        return dict.__len__(self) + len(self._thunks) + (0 if self._done else sum(1 for k in self._lazy if not dict.__contains__(self, k)))
-
-    def copy(self):
-        self._fill()
-        return dict(self)
-
-    def pop(self, k, *default):
-        if k in self:
-            self[k]
-        return dict.pop(self, k, *default)
-
-    def __eq__(self, other):
-        self._fill()
-        return dict.__eq__(self, other)
-
-    __hash__ = None
-
-    def __reduce__(self):
-        self._fill()
-        return (dict, (dict(self),))
+    def _resolve(self, keys=None):
+        for k in tuple(self._thunks) if keys is None else keys:
+            if k in self._thunks:
+                dict.__setitem__(self, k, self._thunks.pop(k)())
+        if self._lazy and (keys is None or not self._lazy.isdisjoint(keys)):
+            self._lazy = frozenset()
+            dict.update(self, self._mat())

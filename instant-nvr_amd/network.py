@@ -150,7 +150,7 @@ class Embedder(nn.Module):
             self.maybe_adopt_batch_bounds(batch)
         keep = []
         g = self.grid_struct(keep)
-        x = xyz.detach().to(torch.float32).contiguous()
+        x = _abi.f32c(xyz)
         out = torch.empty(x.shape[0], self.out_dim, device=x.device, dtype=torch.float32)
         _abi.check(_abi.lib().invr_grid_encode_fwd(C.byref(g), _abi.ptr(x), x.shape[0], _abi.ptr(out), _abi.stream_ptr()))
         return out
@@ -309,8 +309,8 @@ class Network(nn.Module):
         reference.  Training gradients flow through Renderer.render (autograd.py), not through here."""
         L = _abi.lib()
         ctx = batch if isinstance(batch, RenderContext) else self.prepare(batch)
-        x = wpts.detach().to(torch.float32).contiguous()
-        d = viewdir.detach().to(torch.float32).contiguous()
+        x = _abi.f32c(wpts)
+        d = _abi.f32c(viewdir)
         n = x.shape[0]
         raw = torch.empty(n, 4, device=x.device)
         occ = torch.empty(n, device=x.device)
@@ -338,7 +338,7 @@ class Network(nn.Module):
         L = _abi.lib()
         dev = ray_o.device
         ctx = batch if isinstance(batch, RenderContext) else self.prepare(batch)
-        f = lambda t: t.detach().to(torch.float32).contiguous()
+        f = _abi.f32c
         ray_o, ray_d, near, far = f(ray_o), f(ray_d), f(near), f(far)
         n, S = ray_o.shape[0], int(n_samples)
         out = {'z_vals': torch.empty(n, S, device=dev), 'stats': torch.zeros(_abi.STATS_LEN, dtype=torch.int32, device=dev)}
@@ -370,7 +370,7 @@ class Network(nn.Module):
         dev = ray_o.device
         ctx = batch if isinstance(batch, RenderContext) else self.prepare(batch)
         model, scene, keep = ctx.model, ctx.scene, ctx.keep
-        f = lambda t: t.detach().to(torch.float32).contiguous()
+        f = _abi.f32c
         ray_o, ray_d, near, far = f(ray_o), f(ray_d), f(near), f(far)
         n = ray_o.shape[0]
         S = int(n_samples)

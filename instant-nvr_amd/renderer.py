@@ -19,6 +19,7 @@ import torch
 
 from . import _abi
 from .config import cfg as global_cfg, NUM_PARTS
+from .lazyret import LazyDict
 
 MAX_SAMPLES_PER_CALL = (1 << 31) - 1
 
@@ -32,7 +33,6 @@ def dense_train_rows(v, stats, ctx, rays, S, jitter):
         tpts = init_bigpose under that part's 4-NN weights — the reference warps all Na x P rows — through the dense stage
         entry points invr_pose_points -> invr_knn_blend -> invr_warp_deform (Na is a training patch's ~4e4 survivors).
     `stats` is the host copy of the statistics block, `rays` = (ray_o, ray_d, near, far) of the forward, `jitter` its z jitter."""
-    from . import stages
     Na, cap, P = int(stats[0]), v['cap'], NUM_PARTS
     dev = v['pflags'].device
     resd = torch.zeros(Na + 1, P, 3, device=dev)
@@ -54,117 +54,139 @@ def dense_train_rows(v, stats, ctx, rays, S, jitter):
             tocc[fr, p] = tocc[Na, p]
     resd, tpts, tocc = resd[:Na], tpts[:Na], tocc[:Na]
     if Na:
-        ro, rd, nr, fa = rays
-        pts, dirs = stages.pose_points(ctx.scene, ro, rd, nr, fa, S, v['active_idx'][:Na], jitter=jitter)
-        bw, _ = stages.knn_blend(ctx.scene, pts)
-        tp, _, _ = stages.warp_deform(ctx.scene, ctx.model, pts, dirs, bw, torch.zeros(Na, P, dtype=torch.uint8, device=dev))
-        known = (((v['pflags'][:Na].to(torch.int32) | far)[:, None] >> torch.arange(P, device=dev)[None]) & 1).bool()
+        known, tp = unlisted_bigpose(v, Na, far, ctx, rays, S, jitter)
         tpts = torch.where(known[..., None], tpts, tp)
     return resd, tpts, tocc
 
 
-class LazyHostRet(dict):
+def unlisted_bigpose(v, Na, far, ctx, rays, S, jitter):
+    """A (survivor, part) row that is neither listed nor far gets init_bigpose through the dense stage entry points, as the
+    reference computes it for all Na x P rows (inb_part_network_multiassign.py:96-120): -> known (Na, P) bool, True where the pair
+    lists have the row (`far` = the survivors' far flags as int32), and tp (Na, P, 3), init_bigpose of every row."""
+    from . import stages
+    ro, rd, nr, fa = rays
+    dev = far.device
+    pts, dirs = stages.pose_points(ctx.scene, ro, rd, nr, fa, S, v['active_idx'][:Na], jitter=jitter)
+    bw, _ = stages.knn_blend(ctx.scene, pts)
+    tp, _, _ = stages.warp_deform(ctx.scene, ctx.model, pts, dirs, bw, torch.zeros(Na, NUM_PARTS, dtype=torch.uint8, device=dev))
+    known = (((v['pflags'][:Na].to(torch.int32) | far)[:, None] >> torch.arange(NUM_PARTS, device=dev)[None]) & 1).bool()
+    return known, tp
+
+
+def pair_rows(tocc, tpts, resd, noise, deform):
+    """The pair regulariser's rows (inb_renderer.py:78-94, compute_val_pair_around_range :41): of the dense (Na*P, .) train rows,
+    those near the surface, and the deformer's residual at a jittered neighbour of each -> oresd (1, 2 m, 3), the selected resd
+    followed by the neighbours'.  `noise(reg, like)` = uniform [0, 1) draws shaped like the selected points `like` (1, m, 3), `reg`
+    their row indices; `deform(neighbor)` = the residual (1, m, 3) at such points."""
+    reg = ((tocc.detach().reshape(-1) - 0.5).abs() < 0.02).nonzero(as_tuple=True)[0]
+    if not reg.numel():
+        return torch.zeros(1, 0, 3, device=tocc.device)
+    reg_tpts = tpts.reshape(-1, 3)[reg][None]
+    neighbor = reg_tpts + (noise(reg, reg_tpts) - 0.5) * 0.01
+    return torch.cat([resd.reshape(-1, 3)[reg][None], deform(neighbor)], dim=1)
+
+
+# ---- the survivor capacity of an eval frame's workspace ----------------------------------------------------------------------
+# The workspace is ~850 B per possible survivor.  With max_active = 0 every ray-sample may survive (28 GB for 512x512x128), so an
+# eval frame is rendered with a survivor bound taken from the frames before it (`Renderer._cap_hint`); a frame that overflows the
+# bound — stats[6]: nothing was written out of bounds, the frame is just incomplete — is rendered once more at full capacity
+# (max_active = 0), and the hint only grows: every workspace settles at ONE size, the largest frame seen.  (Following every frame's
+# own count made a lane reallocate whenever a denser frame than any before landed on it: a multi-GB hipMalloc, ~1 s each on this
+# runtime, for the first LCM(K, sequence period) frames.)
+CAP_MIN = 65536                     # survivors: the least bound, and the slack on top of a counted frame
+# Head-room over the largest frame seen, per path — measured choices, not to be merged (DESIGN.md "Round 6" row 8: lane memory
+# 176 -> 49 GB; round 5 took 1.5 x in the lanes and 1.25 x on top of it for the first frame: 1.9 x the survivors, 6.5 GB per lane):
+CAP_HEADROOM_SYNC = 1.5             # Renderer.render on the caller's stream (one workspace)
+CAP_HEADROOM_LANE = 1.25            # frames in flight (K workspaces) ...
+CAP_HEADROOM_FIRST = 1.2            # ... times this for the first frame of a sequence, which sizes all K lanes: 1.5 x its survivors in all
+
+
+def cap_bound(n_samp, hint):
+    """survivor bound of a frame of n_samp ray-samples under the hint (None: a quarter of the ray-samples)"""
+    return min(n_samp, max(hint if hint is not None else n_samp // 4, CAP_MIN))
+
+
+def cap_overflowed(stats):
+    return int(stats[6]) != 0
+
+
+def cap_check(stats):
+    if cap_overflowed(stats):
+        raise RuntimeError('invr_render_fwd reported stats[6] = %d: workspace overflow' % int(stats[6]))
+
+
+def cap_grown(hint, stats, headroom):
+    """the hint after a complete frame with the statistics block `stats` (stats[0] = its survivors): grow-only"""
+    return max(hint or 0, int(headroom * int(stats[0])) + CAP_MIN)
+
+
+def _host_copies(dev, pin):
+    """device tensors -> host tensors of the same shapes (page-locked if `pin`), with ONE stream synchronisation for all of them"""
+    host, on_dev = {}, False
+    for k, v in dev.items():
+        v = v.detach()
+        h = torch.empty(v.shape, dtype=v.dtype, device='cpu', pin_memory=pin and v.is_cuda)
+        h.copy_(v, non_blocking=True)
+        on_dev = on_dev or v.is_cuda
+        host[k] = h
+    if on_dev:
+        torch.cuda.current_stream().synchronize()
+    return host
+
+
+class _FrameRet(LazyDict):
+    """An eval return dict whose frame may still be in flight on one of the renderer's lanes (Renderer.in_flight > 1):
+    `pending.result()` joins it — a host wait on THAT frame's event only, which also checks its workspace for overflow — and hands
+    over a pair of dicts; `keys` = the keys the dict will have."""
+    def _in_flight_init(self, pending, keys):
+        self._pending, self._keys = pending, tuple(keys)
+
+    def _join(self):
+        """the pair of a frame joined by this call, else None"""
+        if self._pending is not None:
+            pend, self._pending = self._pending, None
+            return pend.result()
+
+    def in_flight(self):
+        """True while the frame behind this dict has not been joined"""
+        return self._pending is not None and not self._pending.done()
+
+
+class LazyHostRet(_FrameRet):
     """The eval return dict of Renderer.render under the reference's move-everything-to-the-host contract (inb_renderer.py:199-200).
     The image maps (rgb_map, acc_map: what the reference's evaluator and visualizers read, evaluators/if_nerf.py:77,
     visualizers/if_nerf.py:24) are host tensors when render() returns; the per-sample tensors (raw, occ: 656 MB for a 512x512x128
-    frame, 12 ms of PCIe for a 2.5 ms render) are copied on first access — by key, or all of them by keys() / items() / values() /
-    iteration — and are host tensors of the reference's shapes from then on.  The device tensors they come from stay alive inside
-    this object until then; a dict built from it (`dict(ret)`) is the plain all-host dict."""
+    frame, 12 ms of PCIe for a 2.5 ms render) are copied on first access — by key, or all of them by any whole-dict view
+    (lazyret.LazyDict) — and are host tensors of the reference's shapes from then on.  The device tensors they come from stay alive
+    inside this object until then; a dict built from it (`dict(ret)`) is the plain all-host dict."""
     def __init__(self, host, lazy_dev, pin, pending=None, keys=()):
         super().__init__(host)
         self._lazy, self._pin = dict(lazy_dev), pin
-        # a frame still in flight on one of the renderer's lanes (Renderer.in_flight > 1): `pending.result()` joins it — a host wait
-        # on THAT frame's event only — and hands over (host maps, device tensors for the lazy keys); `keys` = the keys it will have
-        self._pending, self._keys = pending, tuple(keys)
+        self._in_flight_init(pending, keys)          # joined: (host maps, device tensors for the lazy keys)
 
-    def _settle(self):
-        if self._pending is not None:
-            pend, self._pending = self._pending, None
-            host, lazy = pend.result()
-            dict.update(self, host)
-            self._lazy = dict(lazy)
+    def _promised(self):
+        return self._keys if self._pending is not None else tuple(self._lazy)
 
-    def _fetch(self, keys):
-        self._settle()
-        todo = [k for k in keys if k in self._lazy]
-        if not todo:
-            return
-        on_dev = False
-        for k in todo:
-            v = self._lazy.pop(k).detach()
-            h = torch.empty(v.shape, dtype=v.dtype, device='cpu', pin_memory=self._pin and v.is_cuda)
-            h.copy_(v, non_blocking=True)
-            on_dev = on_dev or v.is_cuda
-            dict.__setitem__(self, k, h)
-        if on_dev:
-            torch.cuda.current_stream().synchronize()
+    def _fetch(self, keys=None):
+        # join the frame FIRST: while it is in flight `_lazy` is still empty, and "all of them" taken before the join would fetch nothing
+        joined = self._join()
+        if joined is not None:
+            dict.update(self, joined[0])
+            self._lazy = dict(joined[1])
+        todo = [k for k in (self._lazy if keys is None else keys) if k in self._lazy]
+        if todo:
+            dict.update(self, _host_copies({k: self._lazy.pop(k) for k in todo}, self._pin))
 
-    def _fetch_all(self):
-        # join the frame FIRST: while it is in flight `_lazy` is still empty, and tuple(self._lazy) taken before the join would fetch nothing
-        self._settle()
-        self._fetch(tuple(self._lazy))
-
-    def __contains__(self, k):
-        if self._pending is not None:
-            return k in self._keys
-        return dict.__contains__(self, k) or k in self._lazy
-
-    def __getitem__(self, k):
-        self._fetch((k,))
-        return dict.__getitem__(self, k)
-
-    def get(self, k, d=None):
-        return self[k] if k in self else d
-
-    def __len__(self):
-        if self._pending is not None:
-            return len(self._keys)
-        return dict.__len__(self) + len(self._lazy)
-
-    def __iter__(self):
-        self._fetch_all()
-        return dict.__iter__(self)
-
-    def keys(self):
-        self._fetch_all()
-        return dict.keys(self)
-
-    def items(self):
-        self._fetch_all()
-        return dict.items(self)
-
-    def values(self):
-        self._fetch_all()
-        return dict.values(self)
-
-    def pop(self, k, *default):
-        self._fetch((k,))
-        return dict.pop(self, k, *default)
-
-    def copy(self):
-        self._fetch_all()
-        return dict(dict.items(self))           # (the plain all-host dict)
-
-    def __eq__(self, other):
-        self._fetch_all()
-        return dict.__eq__(self, other)
-
-    __hash__ = None
+    _resolve = _fetch
 
     def __repr__(self):
         if self._pending is not None:
             return 'LazyHostRet(<frame in flight: %s>)' % ', '.join(self._keys)
         return 'LazyHostRet(%s%s)' % (dict.__repr__(self), ''.join(', %s: <on the device>' % k for k in self._lazy))
 
-    def __reduce__(self):                       # pickle / copy.deepcopy: the plain all-host dict
-        self._fetch_all()
-        return (dict, (dict(dict.items(self)),))
-
     def pending(self):
         """keys whose host copy has not been made yet"""
-        if self._pending is not None:
-            return tuple(self._keys)
-        return tuple(self._lazy)
+        return tuple(self._promised())
 
     def device_bytes(self):
         """bytes of device memory the not-yet-fetched tensors of a joined frame keep alive (occ is a view of raw: counted once)"""
@@ -179,80 +201,26 @@ class LazyHostRet(dict):
 
     def fetch(self):
         """make every entry a host tensor now (releases the device tensors)"""
-        self._fetch_all()
-
-    def in_flight(self):
-        """True while the frame behind this dict has not been joined (Renderer.in_flight > 1)"""
-        return self._pending is not None and not self._pending.done()
+        self._fetch()
 
 
-class LazyDevRet(dict):
+class LazyDevRet(_FrameRet):
     """The eval return dict of a frame in flight when the outputs stay on the device (Renderer.eval_to_cpu = False with
-    Renderer.in_flight > 1): every access joins the frame first (a host wait on that frame's event, which also checks its workspace
-    for overflow); from then on it is the plain dict of device tensors."""
+    Renderer.in_flight > 1): every access but `in` / len() joins the frame first; from then on it is the plain dict of device tensors."""
     def __init__(self, pending, keys):
         super().__init__()
-        self._pending, self._keys = pending, tuple(keys)
+        self._in_flight_init(pending, keys)          # joined: (the device dict, {})
 
-    def _settle(self):
-        if self._pending is not None:
-            pend, self._pending = self._pending, None
-            dev, _ = pend.result()
-            dict.update(self, dev)
+    def _promised(self):
+        return self._keys if self._pending is not None else ()
 
-    def __contains__(self, k):
-        return k in self._keys if self._pending is not None else dict.__contains__(self, k)
-
-    def __len__(self):
-        return len(self._keys) if self._pending is not None else dict.__len__(self)
-
-    def __getitem__(self, k):
-        self._settle()
-        return dict.__getitem__(self, k)
-
-    def get(self, k, d=None):
-        self._settle()
-        return dict.get(self, k, d)
-
-    def __iter__(self):
-        self._settle()
-        return dict.__iter__(self)
-
-    def keys(self):
-        self._settle()
-        return dict.keys(self)
-
-    def items(self):
-        self._settle()
-        return dict.items(self)
-
-    def values(self):
-        self._settle()
-        return dict.values(self)
-
-    def pop(self, k, *default):
-        self._settle()
-        return dict.pop(self, k, *default)
-
-    def copy(self):
-        self._settle()
-        return dict(self)
-
-    def __eq__(self, other):
-        self._settle()
-        return dict.__eq__(self, other)
-
-    __hash__ = None
+    def _resolve(self, keys=None):
+        joined = self._join()
+        if joined is not None:
+            dict.update(self, joined[0])
 
     def __repr__(self):
         return 'LazyDevRet(<frame in flight: %s>)' % ', '.join(self._keys) if self._pending is not None else dict.__repr__(self)
-
-    def __reduce__(self):
-        self._settle()
-        return (dict, (dict(self),))
-
-    def in_flight(self):
-        return self._pending is not None and not self._pending.done()
 
 
 class _Lane:
@@ -335,21 +303,14 @@ class _PendingFrame:
             return self._res
         r, lane = self.r, self.lane
         self.event.synchronize()
-        redo = bool(self.cap) and int(self.stats_host[6]) != 0
-        if redo:                                                          # survivor bound too small: once more at full capacity
+        if self.cap and cap_overflowed(self.stats_host):                  # survivor bound too small: once more at full capacity
             lane.ws = None                                                # (not both workspaces at once)
             self.out = self._run(0)
             lane.stream.synchronize()
             lane.ws = None          # ~1150 B per ray-sample: the next frame of this lane gets one sized from the new survivor count
         st = self.stats_host.clone()                                      # (the lane's buffer is reused by its next frame)
-        if int(st[6]) != 0:
-            raise RuntimeError('invr_render_fwd reported stats[6] = %d: workspace overflow' % int(st[6]))
-        # grow-only: the K lanes' workspaces settle at ONE size — the largest frame seen — after a few frames.  (Following every
-        # frame's own count made a lane reallocate whenever a denser frame than any before landed on it: a multi-GB hipMalloc,
-        # ~1 s each on this runtime, for the first LCM(K, sequence period) frames.)
-        # (1.25 x the largest frame seen; the FIRST frame of a sequence adds its own head-room in _render_in_flight.  Round 5 took 1.5 x
-        # here and 1.25 x on top of it there: 1.9 x the survivors, 6.5 GB per lane)
-        r._cap_hint = max(r._cap_hint or 0, int(1.25 * int(st[0])) + 65536)
+        cap_check(st)
+        r._cap_hint = cap_grown(r._cap_hint, st, CAP_HEADROOM_LANE)      # (the FIRST frame of a sequence adds its own head-room in _render_in_flight)
         r.last_stats = self.out['stats']
         out = self.out
         cur = torch.cuda.current_stream(out['rgb_map'].device)
@@ -362,18 +323,8 @@ class _PendingFrame:
         if lane.pending is self:
             lane.pending = None
         self.keep = self.call = None           # the frame's inputs may go
-        if r.eval_to_cpu:
-            lazy = {k: dev[k] for k in ('raw', 'occ') if k in dev}
-            maps = LazyHostRet({}, {k: dev[k] for k in ('rgb_map', 'acc_map')}, r.pin_host)          # 4 MB, now: the frame is complete, the
-            maps._fetch(('rgb_map', 'acc_map'))                                                       # other lanes keep rendering beside the copy
-            host = dict(maps)
-            if not r.lazy_host:
-                tmp = LazyHostRet(host, lazy, r.pin_host)
-                tmp._fetch(tuple(lazy))
-                host, lazy = dict(tmp), {}
-            self._res = (host, lazy)
-        else:
-            self._res = (dev, {})
+        # (eval_to_cpu: the maps' 4 MB now — the frame is complete, the other lanes keep rendering beside the copy)
+        self._res = r._host_maps(dev) if r.eval_to_cpu else (dev, {})
         self.out = None
         return self._res
 
@@ -429,27 +380,20 @@ class Renderer:
         for i in range(0, n_pixel, per_call):
             sl = slice(i, i + per_call)
             n_samp = min(per_call, n_pixel - i) * S
-            # The workspace is ~850 B per possible survivor.  With max_active = 0 every ray-sample may survive (28 GB
-            # for 512x512x128); since the eval contract ends in a host copy anyway, the survivor capacity follows the
-            # previous frame (x1.5) and a frame that overflows it (stats[6]) is rendered again at full capacity.
-            cap = 0
-            if self.adaptive_cap and self.eval_to_cpu:
-                cap = min(n_samp, max(self._cap_hint if self._cap_hint is not None else n_samp // 4, 65536))
+            # the survivor bound (cap_bound) applies here only where the eval contract ends in a host copy anyway: reading the
+            # statistics block synchronises.  eval_to_cpu = False: full capacity, and the asynchronous caller checks last_stats[6] itself
+            cap = cap_bound(n_samp, self._cap_hint) if self.adaptive_cap and self.eval_to_cpu else 0
             call = lambda c: self.net.render_rays(batch, ray_o[0, sl], ray_d[0, sl], near[0, sl], far[0, sl], S,
                                                   jitter=None if jitter is None else jitter[sl], want_raw=self.want_raw, max_active=c)
             out = call(cap)
-            if cap:
+            if self.eval_to_cpu:
                 st = out['stats'].cpu()
-                if int(st[6]) != 0:
-                    out = call(0)
-                    st = out['stats'].cpu()
-                self._cap_hint = max(self._cap_hint or 0, int(1.5 * int(st[0])) + 65536)          # grow-only (see _PendingFrame.result)
-            elif self.eval_to_cpu:
-                st = out['stats'].cpu()
-            else:
-                st = None                                   # asynchronous caller: check last_stats[6] yourself
-            if st is not None and int(st[6]) != 0:
-                raise RuntimeError('invr_render_fwd reported stats[6] = %d: workspace overflow' % int(st[6]))
+                if cap:
+                    if cap_overflowed(st):
+                        out = call(0)
+                        st = out['stats'].cpu()
+                    self._cap_hint = cap_grown(self._cap_hint, st, CAP_HEADROOM_SYNC)
+                cap_check(st)
             outs.append(out)
         cat = (lambda k: outs[0][k]) if len(outs) == 1 else (lambda k: torch.cat([o[k] for o in outs], 0))
         ret = {'rgb_map': cat('rgb_map')[None], 'acc_map': cat('acc_map')[None]}
@@ -458,16 +402,20 @@ class Renderer:
             ret['occ'] = cat('occ')[None, :, None]
         self.last_stats = outs[-1]['stats']
         if self.eval_to_cpu:
-            # the reference moves every eval output to the host (:199-200).  raw + occ of a 512x512x128 frame are 656 MB: through
-            # pageable memory that copy takes ~25x the render; page-locked destinations (torch's caching host allocator: fresh
-            # tensors per call, no aliasing between frames) and one stream synchronisation bring it to the PCIe rate
-            # — for the image maps at once, for raw / occ on first access (LazyHostRet; lazy_host = False: all four at once)
-            lazy = {k: ret[k] for k in ('raw', 'occ') if self.lazy_host and k in ret}
-            host = LazyHostRet({}, {k: v for k, v in ret.items() if k not in lazy}, self.pin_host)
-            host._fetch(tuple(host._lazy))
-            host._lazy = lazy
-            ret = self._track_lazy(host) if lazy else host
+            host, lazy = self._host_maps(ret)
+            ret = LazyHostRet(host, lazy, self.pin_host)
+            if lazy:
+                self._track_lazy(ret)
         return ret
+
+    def _host_maps(self, dev):
+        """eval_to_cpu: the reference moves every eval output to the host (:199-200).  raw + occ of a 512x512x128 frame are 656 MB:
+        through pageable memory that copy takes ~25x the render; page-locked destinations (pin_host; torch's caching host allocator:
+        fresh tensors per call, no aliasing between frames) and one stream synchronisation bring it to the PCIe rate — for the image
+        maps now, for raw / occ on first access (lazy_host = False: all four now).
+        The device dict of a complete frame -> (host tensors, device tensors still to copy): the two halves of a LazyHostRet."""
+        lazy = {k: dev[k] for k in ('raw', 'occ') if self.lazy_host and k in dev}
+        return _host_copies({k: v for k, v in dev.items() if k not in lazy}, self.pin_host), lazy
 
     def _render_in_flight(self, batch, ray_o, ray_d, near, far, S, jitter):
         """One eval frame on the next lane (see __init__); returns a dict that joins the frame on first access."""
@@ -480,7 +428,7 @@ class Renderer:
         if lane.pending is not None:
             lane.pending.result()              # the frame rendered here K calls ago (long done): releases its inputs, updates the cap hint
         n_samp = ray_o.shape[0] * S
-        cap = min(n_samp, max(self._cap_hint if self._cap_hint is not None else n_samp // 4, 65536)) if self.adaptive_cap else 0
+        cap = cap_bound(n_samp, self._cap_hint) if self.adaptive_cap else 0         # (the join reads the statistics block either way)
         if lane.ws is not None and lane.ws.numel() < _abi.lib().invr_workspace_bytes(ray_o.shape[0], S, cap):
             # the survivor bound grew past this lane's workspace: give the old block back to the DRIVER before the larger one is
             # allocated — the caching allocator would keep it (a 4 GB block nobody can reuse, per lane and regrowth: 176 GB reserved
@@ -497,11 +445,10 @@ class Renderer:
         if self._cap_hint is None and self.adaptive_cap:
             # the first frame of a sequence is joined at once: its survivor count sizes the workspaces of all later frames (K lanes at
             # the no-hint default of a quarter of the ray-samples would be K x 9.6 GB for 512x512x128)
-            pend.result()
-            if lane.ws is not None and self._cap_hint is not None and cap > 2 * self._cap_hint:
+            pend.result()                                            # (sets the hint, or raises)
+            if cap > 2 * self._cap_hint:
                 lane.ws = None
-            if self._cap_hint is not None:
-                self._cap_hint = int(1.2 * self._cap_hint)           # head-room over the first frame (1.5 x its survivors in all): later frames of a sequence rarely force a regrowth
+            self._cap_hint = int(CAP_HEADROOM_FIRST * self._cap_hint)           # later frames of a sequence rarely force a regrowth
         keys = ('rgb_map', 'acc_map') + (('raw', 'occ') if self.want_raw else ())
         if self.eval_to_cpu:
             return self._track_lazy(LazyHostRet({}, {}, self.pin_host, pending=pend, keys=keys))
@@ -591,20 +538,12 @@ class Renderer:
     def _train_extras(self, net, ctx, ws, stats_dev, n, S, max_active, noise_dense, rays, jitter):
         """resd / tpts / tocc (dense (Na*P, .) layouts in the reference's row order) and oresd from the pair lists of the
         last forward (host read-back of the counts: synchronises)."""
-        cfg = self.cfg
         stats = stats_dev.cpu()
         v = _abi.ws_views(ws, n, S, max_active)
-        dev = ws.device
         resd, tpts, tocc = dense_train_rows(v, stats, ctx, rays, S, jitter)
         out = {'resd': resd.reshape(1, -1, 3), 'tpts': tpts.reshape(1, -1, 3), 'tocc': tocc.reshape(1, -1, 1)}
-        if cfg.use_pair_reg and noise_dense is not None:
-            reg = ((tocc.reshape(-1) - 0.5).abs() < 0.02).nonzero(as_tuple=True)[0]
-            if reg.numel():
-                reg_tpts = tpts.reshape(-1, 3)[reg][None]
-                neighbor = reg_tpts + (noise_dense[reg][None] - 0.5) * 0.01
-                out['oresd'] = torch.cat([resd.reshape(-1, 3)[reg][None], net.resd(neighbor, ctx)], dim=1)
-            else:
-                out['oresd'] = torch.zeros(1, 0, 3, device=dev)
+        if self.cfg.use_pair_reg and noise_dense is not None:                  # (the draw the fused forward used for that row)
+            out['oresd'] = pair_rows(tocc, tpts, resd, lambda reg, like: noise_dense[reg][None], lambda x: net.resd(x, ctx))
         return out
 
     def _render_train(self, batch, jitter):
@@ -625,12 +564,10 @@ class Renderer:
         else:
             out = net.render_rays(ctx, ray_o, ray_d, near, far, S, jitter=jitter, want_raw=True, want_weights=True)
         stats = out['stats'].cpu()                          # host sync, as the reference's nonzero()s
-        assert int(stats[6]) == 0, 'invr workspace overflow'
-        Na = int(stats[0])
+        cap_check(stats)
         ws, _, _, max_active = out['_ws']
         v = _abi.ws_views(ws, n, S, max_active)
-        cap, dev = v['cap'], ray_o.device
-        P = NUM_PARTS
+        dev = ray_o.device
         self.last_stats = out['stats']
         if torch.is_grad_enabled():
             # differentiable recomputation on the pair lists (autograd.py): HIP encoder / compositing
@@ -641,22 +578,12 @@ class Renderer:
         ret = {'rgb_map': out['rgb_map'][None], 'acc_map': out['acc_map'][None], 'raw': out['raw'][None],
                'occ': out['occ'][None, :, None], 'resd': resd.reshape(1, -1, 3), 'tpts': tpts.reshape(1, -1, 3),
                'tocc': tocc.reshape(1, -1, 1)}
-        if cfg.use_pair_reg:                                                             # inb_renderer.py:78-94
-            tflat = tocc.reshape(-1)
-            reg = ((tflat - 0.5).abs() < 0.02).nonzero(as_tuple=True)[0]
-            if reg.numel():
-                reg_tpts = tpts.reshape(-1, 3)[reg][None]
-                reg_resd = resd.reshape(-1, 3)[reg][None]
-                neighbor = reg_tpts + (self._pair_noise(reg_tpts) - 0.5) * 0.01
-                nei = net.resd(neighbor, ctx)
-                ret['oresd'] = torch.cat([reg_resd, nei], dim=1)
-            else:
-                ret['oresd'] = torch.zeros(1, 0, 3, device=dev)
+        if cfg.use_pair_reg:
+            ret['oresd'] = pair_rows(tocc, tpts, resd, lambda reg, like: self._pair_noise(like), lambda x: net.resd(x, ctx))
         if cfg.use_reg_distortion:                                                       # :96-103
             dl = torch.empty(n, device=dev)
             _abi.check(_abi.lib().invr_distortion_fwd(_abi.ptr(out['weights']), _abi.ptr(out['z_vals']), n, S,
                                                       _abi.ptr(dl), _abi.stream_ptr()))
             ret['reg_distortion_loss'] = dl[None]
-        self.last_stats = out['stats']
         self.last_train = {'weights': out['weights'], 'z_vals': out['z_vals']}
         return ret

@@ -13,15 +13,11 @@ from . import _abi
 from .config import NUM_PARTS
 
 
-def _f32(t):
-    return t.detach().to(torch.float32).contiguous()
-
-
 def pose_points(scene, ray_o, ray_d, near, far, n_samples, sample_idx=None, jitter=None, want_dirs=True):
     """get_wsampling_points + world->pose (inb_renderer.py:15-31, blend_utils.py:366-382) of selected ray-samples
     (sample_idx int32 = ray*S + s; None = all, in order) -> pose_pts (n,3), pose_dirs (n,3) — bit-identical to
     what the render kernels compute (same device function)."""
-    ray_o, ray_d, near, far = _f32(ray_o), _f32(ray_d), _f32(near), _f32(far)
+    ray_o, ray_d, near, far = _abi.f32c(ray_o), _abi.f32c(ray_d), _abi.f32c(near), _abi.f32c(far)
     R, S = ray_o.shape[0], int(n_samples)
     if sample_idx is not None:
         sample_idx = sample_idx.to(torch.int32).contiguous()
@@ -32,7 +28,7 @@ def pose_points(scene, ray_o, ray_d, near, far, n_samples, sample_idx=None, jitt
     pts = torch.empty(n, 3, device=dev)
     dirs = torch.empty(n, 3, device=dev) if want_dirs else None
     if jitter is not None:
-        jitter = _f32(jitter)
+        jitter = _abi.f32c(jitter)
     _abi.check(_abi.lib().invr_pose_points(C.byref(scene), _abi.ptr(ray_o), _abi.ptr(ray_d), _abi.ptr(near), _abi.ptr(far),
                                            _abi.ptr(jitter), R, S, _abi.ptr(sample_idx, torch.int32), n, _abi.ptr(pts),
                                            _abi.ptr(dirs), _abi.stream_ptr()))
@@ -41,7 +37,7 @@ def pose_points(scene, ray_o, ray_d, near, far, n_samples, sample_idx=None, jitt
 
 def knn_neighbors(scene, pose_pts):
     """Brute-force per-part 4-NN (blend_utils.py:732-763): -> nn (n,P,4) int32, d2 (n,P,4), w (n,P,4), dist (n,P)."""
-    x = _f32(pose_pts)
+    x = _abi.f32c(pose_pts)
     n, dev = x.shape[0], x.device
     nn = torch.empty(n, NUM_PARTS, 4, dtype=torch.int32, device=dev)
     d2 = torch.empty(n, NUM_PARTS, 4, device=dev)
@@ -54,7 +50,7 @@ def knn_neighbors(scene, pose_pts):
 
 def knn_blend(scene, pose_pts):
     """pts_knn_blend_weights_multiassign_batch (blend_utils.py:817-825): -> bw (n,P,24), dist (n,P)."""
-    x = _f32(pose_pts)
+    x = _abi.f32c(pose_pts)
     n, dev = x.shape[0], x.device
     bw = torch.empty(n, NUM_PARTS, 24, device=dev)
     dist = torch.empty(n, NUM_PARTS, device=dev)
@@ -65,7 +61,7 @@ def knn_blend(scene, pose_pts):
 def warp_deform(scene, model, pose_pts, pose_dirs, bw, flag):
     """Network.pose_points_to_tpose_points (inb_part_network_multiassign.py:77-120), dense over all (point, part) pairs:
     -> tpose (n,P,3), tdirs (n,P,3), resd (n,P,3) (zeros where !flag)."""
-    x, d, bw = _f32(pose_pts), _f32(pose_dirs), _f32(bw)
+    x, d, bw = _abi.f32c(pose_pts), _abi.f32c(pose_dirs), _abi.f32c(bw)
     flag = flag.to(torch.uint8).contiguous()
     n, dev = x.shape[0], x.device
     tp = torch.empty(n, NUM_PARTS, 3, device=dev)
