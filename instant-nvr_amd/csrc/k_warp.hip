@@ -7,9 +7,10 @@
 // (lib/networks/deformers/uv_deformer.py:23-45: UV-volume trilinear -> (u,v,t) -> 8-level F=2
 // grid encoder -> 19-32-32-3 Softplus MLP -> 0.05*tanh).
 //
-// One thread per pair.  The 24 joint matrices and the deformer MLP weights are wave-uniform:
-// they are read through the scalar path (s_load) and used as SGPR operands of v_fmac.
-// The deformer tables are 0.34 MB (L2 resident).
+// Dense stage kernels (k_warp_dense, k_deform_points): one thread per (point, part) / per point; the 24 joint matrices and the
+// deformer MLP weights are wave-uniform there (scalar loads, SGPR operands of v_fmac).  The frame path is ONE kernel over the
+// per-part pair lists, k_deform_pairs: each lane warps its own pair through the pre-blended per-vertex matrices, the wave runs the
+// deformer MLP on the matrix cores.  The deformer tables are 0.34 MB (L2 resident; per-frame slices of them in LDS).
 #include <type_traits>
 #include "deform_mlp.h"
 #include "front_bodies.h"
@@ -97,9 +98,13 @@ int launch_warp_deform_dense(const SceneDev& s, const GridDev& dg, const MlpDev&
 }
 
 // ---- pipeline variant: walks the per-part pair lists --------------------------------------------
-// Two kernels so that neither carries the other's live state (LBS: 24 blend weights + two 3x4
-// matrices; deformer: 19 features + two 32-wide hidden layers): each fits well under 128 VGPRs and
-// runs at >= 4 waves/SIMD instead of the 2 waves/SIMD (256 VGPRs) of the fused form.
+// ONE kernel (k_deform_pairs below): lane j of a wave's 64-pair batch warps its own pair (warp_pair) and the wave then runs the
+// deformer on the batch, 16-pair tiles on the matrix cores.  The two halves use opposite resources — the warp is a dependent gather
+// chain (l_slot -> l_nn / l_w at the slot -> 24 scattered 16-byte rows of vmat) with little arithmetic, the deformer issues VALU +
+// MFMA from LDS tables with an idle vector-memory path — so part of one wave's gather latency hides under the tile loops of the other two
+// waves of its SIMD (profiles/warp_in_deformer.md: 396 us against 125 + 301 us).  As a kernel of its own (one thread per pair, 125 registers) the warp was bound by that gather latency; it also wrote
+// l_x once to have the deformer read it back and write it again.  The 24 rows are gathered in two batches of 12 (warp_pair): all 24
+// in flight cost the slice form its third wave per SIMD (168 registers is the limit).
 // Per-vertex pre-blended matrices (built once per frame, vertex_mats_body in k_front_scene): bw @ A with bw = sum_k w_k pbw[nn_k]
 // is linear in the skinning rows, so  A_bw = sum_k w_k M_A[nn_k]  with  M_A[v] = sum_j pbw[v][j] A_j  (and the same
 // for big_A).  A pair then needs 4 x 96 B gathers and 96 FMAs instead of 4 x 96 B gathers, the 24-wide blend and
@@ -124,6 +129,7 @@ __device__ __forceinline__ void warp_pair(const RenderArgs& a, const Workspace& 
         o[1] = fmaf(wt.w, v3.y, fmaf(wt.z, v2.y, fmaf(wt.y, v1.y, wt.x * v0.y)));
         o[2] = fmaf(wt.w, v3.z, fmaf(wt.z, v2.z, fmaf(wt.y, v1.z, wt.x * v0.z)));
         o[3] = fmaf(wt.w, v3.w, fmaf(wt.z, v2.w, fmaf(wt.y, v1.w, wt.x * v0.w)));
+        if (j == 2) __builtin_amdgcn_sched_barrier(0);     // (rows 3-5 are requested after rows 0-2 are blended: 12 rows live, not 24)
     }
     float pp[3], pd[3];
     sample_pose_point(a, w.active_idx[slot], pp[0], pp[1], pp[2], nullptr, pd);
@@ -135,26 +141,10 @@ __device__ __forceinline__ void warp_pair(const RenderArgs& a, const Workspace& 
     }
 }
 
-__global__ __launch_bounds__(WARP_BLOCK) void k_warp_pairs(RenderArgs a, Workspace w) {
-    const int p = blockIdx.y;
-    const int cnt = w.counters[CNT_PAIRS + p];
-    const float4* __restrict__ vm = w.knn.vmat + (int64_t)p * w.knn.mpad * 6;
-    for (int64_t i = (int64_t)blockIdx.x * WARP_BLOCK + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * WARP_BLOCK) {
-        float xb[3], db[3];
-        warp_pair(a, w, vm, p, i, xb, db);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            w.l_x[p][c * w.lcap + i] = xb[c];                // init_bigpose
-            w.l_d[p][c * w.lcap + i] = db[c];
-        }
-    }
-}
-
-
 // Residual deformer of the pair lists on the fp32 matrix cores (same D^T = W . X^T orientation as
 // k_part_mlp: 16 pairs = the N columns of v_mfma_f32_16x16x4_f32, accumulators of one layer are the B
 // operands of the next; weight image and K order: deform_mlp.h).  A wave handles 64 pairs per iteration:
-//   1. lane j: canonical point of pair j, trilinear (u,v) from the UV volume
+//   1. lane j: warp of pair j (warp_pair: canonical point and view direction, l_d stored), trilinear (u,v) from the UV volume
 //   2. four 16-pair tiles; in tile cb lane (g = lane>>4, col = lane&15) encodes levels 2g and 2g+1 of
 //      pair cb*16+col (no index math duplicated between lanes)
 //   3. 19(20) -> 32 -> 32 on MFMA (10 + 16 instructions per tile), 32 -> 3 head as VALU dots, 0.05*tanh
@@ -211,10 +201,10 @@ __device__ __forceinline__ void lane_level_slice(const float2* S, const LaneSlic
 
 // ONE kernel template; its three instantiations are the launches of launch_warp_pairs.  (Shared at this level on purpose: with the
 // 16-pair tile extracted as a function the compiler simplifies the callee on its own, before it is inlined — `g`, `lane` of unknown
-// range, r3 as memory — and the slice form comes out with 165-168 instead of 152 registers; the body under two __global__ wrappers,
+// range, r3 as memory — and the slice form came out with 165-168 instead of 152 registers (before the warp was folded in); the body under two __global__ wrappers,
 // or the weight staging as a function of its own, reorder its prologue.  This spelling compiles the slice form to the code of the
 // separate kernel it replaces, byte for byte: profiles/deform_one_statement.md.)
-// Occupancy request: three waves per SIMD for the slice form (152 registers); the 3-D gathers keep more state live — two.
+// Occupancy request: three waves per SIMD for the slice form (158 registers with the warp folded in); the 3-D gathers keep more state live — two.
 #define DF_CB 2                         // 16-pair tiles in flight per wave (register budget)
 template <bool SLICE, bool VSMALL>      // VSMALL: the UV volume qualifies for 24-bit index math (volume_is_small, common.h)
 __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(SLICE ? 3 : 2, SLICE ? 3 : 2))) void k_deform_pairs(RenderArgs a, Workspace w, GridDev dg, DfSliceInfo si,
@@ -268,14 +258,19 @@ __global__ __launch_bounds__(DF_BLOCK) __attribute__((amdgpu_waves_per_eu(SLICE 
     const float gb0 = dg.bounds[0], gb1 = dg.bounds[1], gb2 = dg.bounds[2];
     const float ge0 = dg.bounds[3] - gb0, ge1 = dg.bounds[4] - gb1, ge2 = dg.bounds[5] - gb2;
     const float tn = (a.scene.frame_dim[0] - gb2) / ge2;                 // uvt[2] = frame_dim, normalised (:112)
+    const float4* __restrict__ vm = w.knn.vmat + (int64_t)p * w.knn.mpad * 6;
     float* lx = w.l_x[p];
+    float* ld = w.l_d[p];
     float* lr = w.l_r[p];
 
     for (int64_t base = (int64_t)blockIdx.x * DF_BLOCK + wv * 64; base < cnt; base += (int64_t)gridDim.x * DF_BLOCK) {
         const int64_t i = min(base + lane, (int64_t)cnt - 1);
-        float xb[3], uv[2];
+        float xb[3], db[3], uv[2];
+        warp_pair(a, w, vm, p, i, xb, db);                       // (lanes past the list: the last pair again, nothing stored)
+        if (base + lane < cnt) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) xb[c] = lx[c * w.lcap + i];
+            for (int c = 0; c < 3; ++c) ld[c * w.lcap + i] = db[c];
+        }
         sample_volume_dev<2, VSMALL>(a.scene.tuv, 0, xb[0], xb[1], xb[2], uv);
         const float un = (uv[0] - gb0) / ge0, vn = (uv[1] - gb1) / ge1;
         float r3[3] = {0.f, 0.f, 0.f};
@@ -442,10 +437,6 @@ int launch_deform_slice_bwd(const GridDev& dg, const float* frame_dim, const flo
 }
 
 int launch_warp_pairs(const RenderArgs& a, const Workspace& w, const GridDev& dg, const MlpDev& dm, hipStream_t st) {
-    int64_t tiles = cdiv(w.lcap, WARP_BLOCK);
-    unsigned gx = (unsigned)(tiles < 1024 ? (tiles > 0 ? tiles : 1) : 1024);
-    hipLaunchKernelGGL(k_warp_pairs, dim3(gx, INVR_NUM_PARTS), dim3(WARP_BLOCK), 0, st, a, w);
-    INVR_LAUNCH_CHECK();
     int64_t dtiles = cdiv(w.lcap, DF_BLOCK);
     unsigned dgx = (unsigned)(dtiles < 512 ? (dtiles > 0 ? dtiles : 1) : 512);
     DfSliceInfo si;

@@ -73,6 +73,7 @@ struct Workspace {
     int32_t* l_slot[INVR_NUM_PARTS];      // cap
     int32_t* l_nn[INVR_NUM_PARTS];        // cap*4 : neighbour rows inside part_pbw[p]
     float* l_w[INVR_NUM_PARTS];           // cap*4 : normalised gaussian weights
+    // (all three written once, by k_deform_pairs, entries [0, count) only; init_bigpose is never stored: consumers take l_x - l_r)
     float* l_x[INVR_NUM_PARTS];           // 3*cap : canonical (big-pose + residual) xyz, SoA
     float* l_d[INVR_NUM_PARTS];           // 3*cap : canonical view dir, SoA
     float* l_r[INVR_NUM_PARTS];           // 3*cap : residual deformation (resd), SoA
