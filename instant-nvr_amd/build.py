@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'libinvr.so')
-SOURCES = ['invr_abi.hip', 'k_cull.hip', 'k_knn.hip', 'k_warp.hip', 'k_encode.hip', 'k_mlp.hip', 'k_composite.hip', 'k_rays.hip', 'k_prep.hip', 'k_optim.hip', 'k_mlp_bwd.hip', 'k_train.hip', 'k_metrics.hip', 'k_perceptual.hip', 'k_mesh.hip', 'k_batch.hip', 'k_sample.hip']
+SOURCES = ['invr_abi.hip', 'k_cull.hip', 'k_knn.hip', 'k_lists.hip', 'k_warp.hip', 'k_encode.hip', 'k_mlp.hip', 'k_composite.hip', 'k_rays.hip', 'k_prep.hip', 'k_optim.hip', 'k_mlp_bwd.hip', 'k_train.hip', 'k_metrics.hip', 'k_perceptual.hip', 'k_mesh.hip', 'k_batch.hip', 'k_sample.hip']
 INCLUDE = os.path.join(HERE, '..', 'include')
 
 

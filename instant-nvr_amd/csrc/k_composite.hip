@@ -7,7 +7,7 @@
 // source with S a multiple of 64: one wave per CMP_GROUP rays, live passes only): transmittance is an exclusive product
 // scan done with 6 wave shuffles, rgb/acc are wave reductions.  The merge is done on the fly from
 // the per-(slot,part) results, so the (N,4) raw tensor is only written when the caller wants it.
-#include "pipeline.h"
+#include "pair_lists.h"
 
 #define CMP_BLOCK 256
 typedef float cmp_v4 __attribute__((ext_vector_type(4)));
@@ -49,7 +49,7 @@ struct MergedRaw {     // merge per-part results of the survivor slot of sample 
     const int32_t* byte_off;             // windowed order (Workspace::ord_rows > 0): rank of the first survivor of every mask byte; else NULL
     const uint8_t* wsel;                 // the merge's choice per survivor (k_winner_lists)
     const float4* rgbw;                  // [rgb, occ] of the winning listed pair at the survivor's slot; far constants at [lcap + p]
-    int64_t const_slot;
+    int64_t const_slot;                  // Workspace::cap (pair_lists.h: the far-constant rule)
     __device__ __forceinline__ float4 get(int64_t i) const { return get_m(i, mask[i >> 6]); }
     __device__ __forceinline__ float4 get_m(int64_t i, unsigned long long m) const {          // m = mask[i >> 6]
         const int bit = (int)(i & 63);
@@ -63,8 +63,8 @@ struct MergedRaw {     // merge per-part results of the survivor slot of sample 
         if (slot >= 0) {
             // argmax over the 5 parts with zeros for unflagged parts, first maximum wins (:253-255): decided by k_winner_lists
             const unsigned sel = wsel[slot];
-            if (sel < (unsigned)INVR_NUM_PARTS) best = rgbw[slot];
-            else if (sel < 16u) best = rgbw[const_slot + 1 + (sel - 8u)];      // far pair: per-part constant
+            if (wsel_is_listed(sel)) best = rgbw[slot];
+            else if (!wsel_is_none(sel)) best = rgbw[far_result_index(const_slot, wsel_far_part(sel))];      // far pair: per-part constant
         }
         return best;
     }

@@ -542,7 +542,7 @@ __device__ void knn_pairs_bf(const RenderArgs& a, const Workspace& w, float4* sv
 struct KnnLds { int voff[INVR_NUM_PARTS], coff[INVR_NUM_PARTS], soff[INVR_NUM_PARTS], len[INVR_NUM_PARTS]; };
 
 // Outputs per survivor slot: pflags / farflags bytes and, for every flagged part, the 4 neighbour rows and weights at
-// l_nn[p][slot] / l_w[p][slot]; k_pair_lists then builds the dense per-part lists of flagged slots.  (The lists used to be
+// l_nn[p][slot] / l_w[p][slot]; k_pair_lists (k_lists.hip) then builds the dense per-part lists of flagged slots.  (The lists used to be
 // appended here, aggregated per 1024-point workgroup tile: the two barriers per tile made every wave wait for the slowest of
 // the 16 — 64 consecutive survivors are one depth slab of a few rays (ray-major order: depth segments of a few rays), and they differ widely in how many parts they
 // come near — 29 % of the kernel's wave time on a whole frame and 51 % on a 1/8 shard, tools/knn_phase_prof.py.  Now a wave
@@ -826,82 +826,6 @@ __global__ __launch_bounds__(KNN_T) void k_knn_pairs(RenderArgs a, Workspace w) 
     // other kernels are what produced the wrong lanes of profiles/r6_replay_mismatch.md in k_warp_pairs; this kernel never showed
     // them (0 differing neighbour rows / weights in 30,000 stressed frames), and the barrier keeps it that way by construction.
     __syncthreads();
-}
-
-// The per-part pair lists from the flag bytes k_knn_pairs left per survivor: l_slot[p][0..count) = the survivors flagged for
-// part p, ASCENDING (a deterministic order: consecutive pairs are neighbours in space, k_cull.hip); neighbours and weights stay
-// where the KNN wrote them — at the survivor's slot.  One workgroup per group of PAIR_GROUP slots; its list offsets are the sums
-// of the per-group counts the KNN accumulated (gcount) over the groups before it — no atomics here (device-scope atomics on one
-// address serialise at tens of ns each on the 8-XCD part: 1167 claims per part cost this kernel 90 us).  The workgroup of the
-// last group appends one zero-weight pair per part behind the real ones — its field value is the constant every far pair of
-// that part takes (header comment); it lives in the extra slot `cap` — and exports the counters (no extra launches).
-#define PL_BLOCK 256
-#define PL_PER 8
-__global__ __launch_bounds__(PL_BLOCK) void k_pair_lists(Workspace w, int32_t* __restrict__ stats) {
-    __shared__ int s_cnt[PL_BLOCK / 64][INVR_NUM_PARTS];
-    __shared__ int s_red[PL_BLOCK / 64][INVR_NUM_PARTS];
-    const int na = w.counters[CNT_ACTIVE];
-    const int64_t g = blockIdx.x, g_last = (max(na, 1) - 1) / PAIR_GROUP;
-    if (g > g_last) return;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    // list offsets of this group = counts of the groups before it
-    int base[INVR_NUM_PARTS];
-    {
-        int acc[INVR_NUM_PARTS] = {0, 0, 0, 0, 0};
-        for (int64_t q = threadIdx.x; q < g; q += PL_BLOCK)
-#pragma unroll
-            for (int p = 0; p < INVR_NUM_PARTS; ++p) acc[p] += w.gcount[q * INVR_NUM_PARTS + p];
-#pragma unroll
-        for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-            acc[p] = __builtin_amdgcn_readlane(wave_incl_sum_i(acc[p]), 63);
-            if (lane == 0) s_red[wv][p] = acc[p];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-            base[p] = 0;
-            for (int k = 0; k < PL_BLOCK / 64; ++k) base[p] += s_red[k][p];
-        }
-    }
-    for (int64_t t0 = g * PAIR_GROUP; t0 < min((g + 1) * (int64_t)PAIR_GROUP, (int64_t)na); t0 += PL_BLOCK * PL_PER) {
-        // thread -> PL_PER consecutive survivors (one 8-byte load of flag bytes); ranks: inside the thread, the wave, the block
-        const int64_t s0 = t0 + (int64_t)threadIdx.x * PL_PER;
-        unsigned long long fb = 0ull;
-        if (s0 + PL_PER <= na) fb = *reinterpret_cast<const unsigned long long*>(w.pflags + s0);
-        else for (int k = 0; k < PL_PER; ++k) if (s0 + k < na) fb |= (unsigned long long)w.pflags[s0 + k] << (8 * k);
-        int pre[INVR_NUM_PARTS];
-#pragma unroll
-        for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-            const int mine = __popcll(fb & (0x0101010101010101ull << p));
-            const int x = wave_incl_sum_i(mine);
-            pre[p] = x - mine;
-            if (lane == 63) s_cnt[wv][p] = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-            int pos = base[p] + pre[p];
-            for (int k = 0; k < PL_BLOCK / 64; ++k) { const int c = s_cnt[k][p]; if (k < wv) pos += c; base[p] += c; }
-            for (int k = 0; k < PL_PER; ++k)
-                if ((fb >> (8 * k + p)) & 1ull) w.l_slot[p][pos++] = (int32_t)(s0 + k);
-        }
-        __syncthreads();                 // s_cnt is reused by the next tile
-    }
-    if (g != g_last) return;
-    // epilogue: base[] = the totals
-    if (threadIdx.x < INVR_NUM_PARTS) {
-        const int p = threadIdx.x;
-        int tot = 0;
-#pragma unroll
-        for (int q = 0; q < INVR_NUM_PARTS; ++q) if (q == p) tot = base[q];
-        w.l_slot[p][tot] = (int32_t)w.cap;
-        reinterpret_cast<int4*>(w.l_nn[p])[w.cap] = make_int4(0, 0, 0, 0);
-        reinterpret_cast<float4*>(w.l_w[p])[w.cap] = make_float4(0.f, 0.f, 0.f, 0.f);
-        w.counters[CNT_PAIRS + p] = tot + 1;
-        if (p == 0) w.active_idx[w.cap] = 0;
-    }
-    __syncthreads();
-    if (stats && threadIdx.x < INVR_STATS_LEN) stats[threadIdx.x] = threadIdx.x < CNT_LEN ? w.counters[threadIdx.x] : 0;
 }
 
 // Per-frame classification of the distance-volume lattice cells (after k_front_scene, which builds the index): for every cell
@@ -1303,7 +1227,5 @@ int launch_knn_pairs(const RenderArgs& a, const Workspace& w, int32_t* stats, hi
     unsigned grid = (unsigned)(tiles < 256 * 16 ? (tiles > 0 ? cdiv(tiles, 16) : 1) : 256);
     hipLaunchKernelGGL(k_knn_pairs, dim3(grid), dim3(KNN_T), lds_bytes, st, a, w);
     INVR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_pair_lists, dim3((unsigned)w.n_groups), dim3(PL_BLOCK), 0, st, w, stats);
-    INVR_LAUNCH_CHECK();
-    return 0;
+    return launch_pair_lists(w, stats, st);
 }

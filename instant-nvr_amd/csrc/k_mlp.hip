@@ -19,6 +19,7 @@
 #include "pipeline.h"
 
 #include "mlp_common.h"
+#include "pair_lists.h"
 
 // One 16-pair column block of a wave: inputs, activations and outputs stay in registers from the embedding to [rgb, occ].
 struct MlpCol {
@@ -130,8 +131,6 @@ __device__ __forceinline__ float4 st_head(const float* lds, int g, const MlpCol&
 // matrix / vector instruction mix of the colour-MLP regions below (bf16 x 3: 48 MFMAs of 16 cycles + the split of the next inputs)
 #define RGB_MFMAS 48
 #define RGB_V 3
-#define RGB_MFMAS_IN 48
-#define RGB_V_IN 3
 // Interleave directive for one scheduling region (between two MLP_FENCEs): N_MFMA groups of {1 matrix instruction, V vector
 // instructions} — the vector work of the other column block is issued in the shadows of this block's MFMAs (<= 5 single-issue
 // VALU fit beside a 32-cycle fp32 MFMA; MI355X_MICROARCH.md).  LDS reads of the weights float freely.
@@ -144,82 +143,90 @@ __device__ __forceinline__ void mlp_interleave() {
     }
 }
 
+// The skewed two-column schedule, stated once: each region between two MLP_FENCEs pairs the matrix work of one column block with the
+// vector work of the other.  occ_stages: 19 -> 64 -> 17 of A and B.  RGB_FOLLOWS (the one-kernel form): the last region, B's second
+// layer, also forms A's colour inputs; the occupancy phase alone closes it with B's MFMAs only.
+template <bool RGB_FOLLOWS>
+__device__ __forceinline__ void occ_stages(const float* lds, int lane, int g, float fmul, MlpCol& A, MlpCol& B) {
+    st_occ1(lds, lane, g, A);
+    MLP_FENCE();
+    st_occ1(lds, lane, g, B); st_act(A);
+    mlp_interleave<20, 4>();
+    MLP_FENCE();
+    st_occ2(lds, lane, g, A); st_act(B);
+    mlp_interleave<16, 5>();
+    MLP_FENCE();
+    st_occ2(lds, lane, g, B);
+    if (RGB_FOLLOWS) { st_rgb_in(A, g, fmul); mlp_interleave<16, 4>(); }
+    MLP_FENCE();
+}
+// rgb_stages: 70 -> 64 (-> 64) -> 3 of A and B from their embedding, view direction, features and occupancy -> [rgb, occ].
+// A_READY: A's colour inputs were formed by occ_stages<true>; the colour phase alone forms them in a region of their own.
+template <int NRGB, bool A_READY>
+__device__ __forceinline__ void rgb_stages(const float* lds, int lane, int g, float fmul, MlpCol& A, MlpCol& B, float4& rA, float4& rB) {
+    if (!A_READY) { st_rgb_in(A, g, fmul); MLP_FENCE(); }
+    st_rgb1(lds, lane, g, A); st_rgb_in(B, g, fmul);
+    mlp_interleave<RGB_MFMAS, RGB_V>();
+    MLP_FENCE();
+    st_rgb1(lds, lane, g, B);
+    if (NRGB == 3) st_act_split(A); else st_act(A);
+    mlp_interleave<RGB_MFMAS, RGB_V>();
+    MLP_FENCE();
+    if (NRGB == 3) {
+        st_rgb2(lds, lane, g, A); st_act_split(B);
+        mlp_interleave<RGB_MFMAS, RGB_V>();
+        MLP_FENCE();
+        st_rgb2(lds, lane, g, B); st_act(A);
+        mlp_interleave<RGB_MFMAS, 1>();
+        MLP_FENCE();
+    }
+    rA = st_head(lds, g, A); st_act(B);
+    MLP_FENCE();
+    rB = st_head(lds, g, B);
+}
+// a column block takes the (pre-loaded) inputs of its next pair
+template <bool DIRS>
+__device__ __forceinline__ void set_in(MlpCol& c, const MlpIn& in) {
+#pragma unroll
+    for (int s = 0; s < EMB_STEPS; ++s) c.eb[s] = in.eb[s];
+    if (DIRS) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c.dv[k] = in.dv[k];
+    }
+}
+
 template <int NRGB>
 __device__ __forceinline__ void mlp_part(float* lds, const PartMlpDev& pm, const float* __restrict__ emb,
                                          const float* __restrict__ ds, int64_t stride,
                                          int cnt, int64_t cap, float4* __restrict__ raw_direct, const int vblock, const int nblocks) {
-    if ((int64_t)vblock * (MLP_BLOCK / 64) * MLP_CB * 16 >= cnt) return;
+    if ((int64_t)vblock * MLP_PAIRS_PER_WG >= cnt) return;
     __syncthreads();                                   // previous part's weights no longer in use
     stage_weights<NRGB, true>(pm, lds);
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
     const float fmul = (float)(1 << g);                          // frequency 2^g of this lane group
 
-    const int64_t per_block = (MLP_BLOCK / 64) * MLP_CB * 16, step = (int64_t)nblocks * per_block;
-    auto load_in = [&](int64_t wbase, MlpCol& A, MlpCol& B) {
-        const int64_t pa = min(wbase + col, (int64_t)cnt - 1), pb = min(wbase + 16 + col, (int64_t)cnt - 1);
-#pragma unroll
-        for (int s = 0; s < EMB_STEPS; ++s) { A.eb[s] = emb[(int64_t)(4 * s + g) * cap + pa]; B.eb[s] = emb[(int64_t)(4 * s + g) * cap + pb]; }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { A.dv[c] = ds[(int64_t)c * stride + pa]; B.dv[c] = ds[(int64_t)c * stride + pb]; }
+    const int64_t per_block = MLP_PAIRS_PER_WG, step = (int64_t)nblocks * per_block;
+    auto load_in = [&](int64_t wbase, MlpIn (&in)[2]) {
+        load_mlp_in<true>(in, emb, cap, ds, stride, {min(wbase + col, (int64_t)cnt - 1), min(wbase + 16 + col, (int64_t)cnt - 1)}, g);
     };
     int64_t wbase = (int64_t)vblock * per_block + (int64_t)wv * MLP_CB * 16;
     if (wbase >= cnt) return;
     MlpCol A, B;
-    float nA_eb[EMB_STEPS], nB_eb[EMB_STEPS], nA_dv[3], nB_dv[3];      // inputs of the NEXT tile: loaded a whole tile ahead
-    load_in(wbase, A, B);
+    MlpIn nx[2];                                       // inputs of the NEXT tile: loaded a whole tile ahead
+    load_in(wbase, nx);
+    set_in<true>(A, nx[0]); set_in<true>(B, nx[1]);
     for (; wbase < cnt; wbase += step) {
-        {
-            MlpCol tA, tB;
-            load_in(min(wbase + step, (int64_t)cnt - 1), tA, tB);         // (clamped: the values are unused past the last tile)
-#pragma unroll
-            for (int s = 0; s < EMB_STEPS; ++s) { nA_eb[s] = tA.eb[s]; nB_eb[s] = tB.eb[s]; }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { nA_dv[c] = tA.dv[c]; nB_dv[c] = tB.dv[c]; }
-        }
-        st_occ1(lds, lane, g, A);
-        MLP_FENCE();
-        st_occ1(lds, lane, g, B); st_act(A);
-        mlp_interleave<20, 4>();
-        MLP_FENCE();
-        st_occ2(lds, lane, g, A); st_act(B);
-        mlp_interleave<16, 5>();
-        MLP_FENCE();
-        st_occ2(lds, lane, g, B); st_rgb_in(A, g, fmul);
-        mlp_interleave<16, 4>();
-        MLP_FENCE();
-        st_rgb1(lds, lane, g, A); st_rgb_in(B, g, fmul);
-        mlp_interleave<RGB_MFMAS_IN, RGB_V_IN>();
-        MLP_FENCE();
-        st_rgb1(lds, lane, g, B);
-        if (NRGB == 3) st_act_split(A); else st_act(A);
-        mlp_interleave<RGB_MFMAS, RGB_V>();
-        MLP_FENCE();
+        load_in(min(wbase + step, (int64_t)cnt - 1), nx);                 // (clamped: the values are unused past the last tile)
+        occ_stages<true>(lds, lane, g, fmul, A, B);
         float4 rA, rB;
-        if (NRGB == 3) {
-            st_rgb2(lds, lane, g, A); st_act_split(B);
-            mlp_interleave<RGB_MFMAS, RGB_V>();
-            MLP_FENCE();
-            st_rgb2(lds, lane, g, B); st_act(A);
-            mlp_interleave<RGB_MFMAS, 1>();
-            MLP_FENCE();
-            rA = st_head(lds, g, A); st_act(B);
-            MLP_FENCE();
-            rB = st_head(lds, g, B);
-        } else {
-            rA = st_head(lds, g, A); st_act(B);
-            MLP_FENCE();
-            rB = st_head(lds, g, B);
-        }
+        rgb_stages<NRGB, true>(lds, lane, g, fmul, A, B, rA, rB);
         const int64_t pa = wbase + col, pb = wbase + 16 + col;
         if (g == 0) {
             if (pa < cnt) raw_direct[pa] = rA;
             if (pb < cnt) raw_direct[pb] = rB;
         }
-#pragma unroll
-        for (int s = 0; s < EMB_STEPS; ++s) { A.eb[s] = nA_eb[s]; B.eb[s] = nB_eb[s]; }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { A.dv[c] = nA_dv[c]; B.dv[c] = nB_dv[c]; }
+        set_in<true>(A, nx[0]); set_in<true>(B, nx[1]);
     }
 }
 
@@ -241,7 +248,7 @@ __global__ __launch_bounds__(MLP_BLOCK, 3) void k_part_mlp(PartMlpDev pm, const 
 // 9.3 k (leg, arms) of a pair's 22.1 k / 14.0 kFLOP, for 49 % of the pairs of the bench frame.  So the part MLPs run in two
 // phases with identical results:
 //   k_part_occ_all    every listed pair: 19 -> 64 -> 17, occupancy to occp[p][pair], the 16 geometry features to feat[p][pair]
-//   k_winner_lists    per survivor the arg-max over {listed occupancies, far constants, 0 for unflagged parts} -> wsel[slot];
+//   k_winner_lists    (k_lists.hip) per survivor the arg-max over {listed occupancies, far constants, 0 for unflagged parts} -> wsel[slot];
 //                     the winning LISTED pairs (+ the far-constant pair of every part) as per-part lists, segmented by slot group
 //   k_part_rgb_all    70 -> 64 (-> 64) -> 3 on the winners only; [rgb, occ] to rgbw[slot] (far constants: rgbw[lcap + p])
 // A pair's arithmetic does not depend on its column or tile, so both phases reproduce the one-kernel results bit for bit.
@@ -249,39 +256,28 @@ __global__ __launch_bounds__(MLP_BLOCK, 3) void k_part_mlp(PartMlpDev pm, const 
 #define OCC_LDS_FLOATS O_W_RGB1
 __device__ __forceinline__ void occ_part(float* lds, const PartMlpDev& pm, const float* __restrict__ emb, int cnt, int64_t cap,
                                          float* __restrict__ occp, float4* __restrict__ feat, const int vblock, const int nblocks) {
-    const int64_t per_block = (MLP_BLOCK / 64) * MLP_CB * 16, step = (int64_t)nblocks * per_block;
+    const int64_t per_block = MLP_PAIRS_PER_WG, step = (int64_t)nblocks * per_block;
     if ((int64_t)vblock * per_block >= cnt) return;
     __syncthreads();                                   // previous part's weights no longer in use
     stage_weights<2, true, 1>(pm, lds);
     __syncthreads();
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
-    auto load_in = [&](int64_t wbase, float* ea, float* eb) {
-        const int64_t pa = min(wbase + col, (int64_t)cnt - 1), pb = min(wbase + 16 + col, (int64_t)cnt - 1);
-#pragma unroll
-        for (int s = 0; s < EMB_STEPS; ++s) { ea[s] = emb[(int64_t)(4 * s + g) * cap + pa]; eb[s] = emb[(int64_t)(4 * s + g) * cap + pb]; }
+    auto load_in = [&](int64_t wbase, MlpIn (&in)[2]) {
+        load_mlp_in<false>(in, emb, cap, nullptr, 0, {min(wbase + col, (int64_t)cnt - 1), min(wbase + 16 + col, (int64_t)cnt - 1)}, g);
     };
     int64_t wbase = (int64_t)vblock * per_block + (int64_t)wv * MLP_CB * 16;
     if (wbase >= cnt) return;
     MlpCol A, B;
-    float nA[EMB_STEPS], nB[EMB_STEPS];                // inputs of the NEXT tile: loaded a whole tile ahead
-    load_in(wbase, A.eb, B.eb);
+    MlpIn nx[2];                                       // inputs of the NEXT tile: loaded a whole tile ahead
+    load_in(wbase, nx);
+    set_in<false>(A, nx[0]); set_in<false>(B, nx[1]);
     for (; wbase < cnt; wbase += step) {
-        load_in(min(wbase + step, (int64_t)cnt - 1), nA, nB);
-        st_occ1(lds, lane, g, A);
-        MLP_FENCE();
-        st_occ1(lds, lane, g, B); st_act(A);
-        mlp_interleave<20, 4>();
-        MLP_FENCE();
-        st_occ2(lds, lane, g, A); st_act(B);
-        mlp_interleave<16, 5>();
-        MLP_FENCE();
-        st_occ2(lds, lane, g, B);
-        MLP_FENCE();
+        load_in(min(wbase + step, (int64_t)cnt - 1), nx);
+        occ_stages<false>(lds, lane, g, 0.0f, A, B);
         const int64_t pa = wbase + col, pb = wbase + 16 + col;
         if (pa < cnt) { feat[pa * 4 + g] = make_float4(A.feat[0], A.feat[1], A.feat[2], A.feat[3]); if (g == 0) occp[pa] = A.occ; }
         if (pb < cnt) { feat[pb * 4 + g] = make_float4(B.feat[0], B.feat[1], B.feat[2], B.feat[3]); if (g == 0) occp[pb] = B.occ; }
-#pragma unroll
-        for (int s = 0; s < EMB_STEPS; ++s) { A.eb[s] = nA[s]; B.eb[s] = nB[s]; }
+        set_in<false>(A, nx[0]); set_in<false>(B, nx[1]);
     }
 }
 
@@ -298,264 +294,26 @@ __device__ __forceinline__ bool part_range(const int64_t* tiles, int64_t total, 
     else { if (b != min(start, G - 1)) return false; vb = 0; nb = 1; }
     return true;
 }
-
-__global__ __launch_bounds__(MLP_BLOCK, 4) void k_part_occ_all(MlpAllArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[OCC_LDS_FLOATS];
-    const int per_block = (MLP_BLOCK / 64) * MLP_CB * 16, G = (int)gridDim.x, b = (int)blockIdx.x;
-    int64_t tiles[INVR_NUM_PARTS], total = 0;
-    for (int p = 0; p < INVR_NUM_PARTS; ++p) { tiles[p] = (a.counts[p] + per_block - 1) / per_block; total += tiles[p]; }
+// body(p, vb, nb) for every part p this workgroup serves, given the parts' (cost-weighted) tile counts
+template <class Body>
+__device__ __forceinline__ void for_my_parts(const int64_t* tiles, Body body) {
+    const int G = (int)gridDim.x, b = (int)blockIdx.x;
+    int64_t total = 0;
+    for (int p = 0; p < INVR_NUM_PARTS; ++p) total += tiles[p];
     if (total == 0) return;
     for (int p = 0; p < INVR_NUM_PARTS; ++p) {
         int vb, nb;
         if (!part_range(tiles, total, p, b, G, vb, nb)) continue;
-        occ_part(lds, a.pm[p], a.emb[p], a.counts[p], a.cap, a.occp[p], a.feat[p], vb, nb);
+        body(p, vb, nb);
     }
 }
 
-// The merge of one survivor = arg-max of the occupancies over the five parts, zeros for unflagged parts, the first maximum wins
-// (inb_part_network_multiassign.py:229-256 with cfg.aggr == ""), evaluated here from the phase-1 occupancies; the survivors whose
-// winner is a LISTED pair are what the colour MLP still has to see.  One workgroup per group of PAIR_GROUP survivor slots — the
-// layout of k_pair_lists: the pairs of group g sit at [off_g, off_g + gcount[g][p]) of part p's list, off_g = the counts of the
-// groups before it — which writes its winners, ascending, to wl[p][off_g ...) and their number to wcnt[g][p]: no global offsets,
-// no atomics; k_part_rgb_all walks the segments.  The last group appends the far-constant pair of every part.
-//
-// cfg.aggr == 'mean' (:236-239; InvrScene::aggr = INVR_AGGR_MEAN): the merged raw is the mean over the five parts of (rgb, occ), zeros
-// for unflagged parts, so every listed pair needs its colour.  The phases then run as
-//   k_part_occ_all -> k_all_lists (wl = identity, wcnt = gcount: every pair "wins") -> k_part_rgb_all ([rgb, occ] per PAIR to
-//   feat[p][pair * 4]) -> k_winner_lists<true>: the same rank walk as the arg-max merge, but it sums the listed / far-constant
-//   values of a survivor in part order, divides by 5 and writes rgbw[slot] (wsel = 0: "read rgbw[slot]").
-#define WL_BLOCK 512         // x WL_PER = PAIR_GROUP: one pass per group (the kernel is a chain of dependent round trips)
-#define WL_PER 8
-// cfg.aggr == 'dist' (:240-244, MODE 2): the 'mean' flow with the parts weighted by F.normalize(1 / (part_dist + 1e-5)) (L2 over the five
-// parts, eps 1e-12) instead of 1 / 5 — part_dist of every (slot, part) from k_knn_pdist.  cfg.aggr == 'mindist' (:245-251, MODE 3): the
-// arg-max flow with the winner = the part of smallest part_dist (first minimum), whatever its occupancy — its listed pair, its far
-// constant, or zeros when that part is not flagged for the survivor.
-template <int MODE>          // 0 = max occupancy, 1 = mean, 2 = dist, 3 = mindist (InvrScene::aggr)
-__global__ __launch_bounds__(WL_BLOCK) void k_winner_lists(Workspace w) {
-    constexpr bool MEAN = MODE == 1 || MODE == 2;
-    __shared__ int s_cnt[WL_BLOCK / 64][INVR_NUM_PARTS];
-    __shared__ int s_red[WL_BLOCK / 64][INVR_NUM_PARTS];
-    const int na = w.counters[CNT_ACTIVE];
-    const int64_t g = blockIdx.x, g_last = (max(na, 1) - 1) / PAIR_GROUP;
-    if (g > g_last) return;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int base[INVR_NUM_PARTS], wbase[INVR_NUM_PARTS], cidx[INVR_NUM_PARTS];
-    {
-        int acc[INVR_NUM_PARTS] = {0, 0, 0, 0, 0};
-        for (int64_t q = threadIdx.x; q < g; q += WL_BLOCK)
-#pragma unroll
-            for (int p = 0; p < INVR_NUM_PARTS; ++p) acc[p] += w.gcount[q * INVR_NUM_PARTS + p];
-#pragma unroll
-        for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-            acc[p] = __builtin_amdgcn_readlane(wave_incl_sum_i(acc[p]), 63);
-            if (lane == 0) s_red[wv][p] = acc[p];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-            base[p] = 0;
-            for (int k = 0; k < WL_BLOCK / 64; ++k) base[p] += s_red[k][p];
-            wbase[p] = 0;
-            cidx[p] = w.counters[CNT_PAIRS + p] - 1;               // list index of the part's far-constant pair
-        }
-    }
-    const int pbase0[INVR_NUM_PARTS] = {base[0], base[1], base[2], base[3], base[4]};
-    for (int64_t t0 = g * PAIR_GROUP; t0 < min((g + 1) * (int64_t)PAIR_GROUP, (int64_t)na); t0 += WL_BLOCK * WL_PER) {
-        const int64_t s0 = t0 + (int64_t)threadIdx.x * WL_PER;
-        unsigned long long fb = 0ull, ffb = 0ull;
-        if (s0 + WL_PER <= na) {
-            fb = *reinterpret_cast<const unsigned long long*>(w.pflags + s0);
-            ffb = *reinterpret_cast<const unsigned long long*>(w.farflags + s0);
-        } else
-            for (int k = 0; k < WL_PER; ++k) if (s0 + k < na) { fb |= (unsigned long long)w.pflags[s0 + k] << (8 * k); ffb |= (unsigned long long)w.farflags[s0 + k] << (8 * k); }
-        // list index of this thread's first pair of every part: ranks inside the thread, the wave, the block (= k_pair_lists)
-        int pos[INVR_NUM_PARTS];
-#pragma unroll
-        for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-            const int mine = __popcll(fb & (0x0101010101010101ull << p));
-            const int x = wave_incl_sum_i(mine);
-            pos[p] = x - mine;
-            if (lane == 63) s_cnt[wv][p] = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-            pos[p] += base[p];
-            for (int k = 0; k < WL_BLOCK / 64; ++k) { const int c = s_cnt[k][p]; if (k < wv) pos[p] += c; base[p] += c; }
-        }
-        __syncthreads();                 // s_cnt is reused below
-        // the merge of the thread's WL_PER survivors.  All occupancies are fetched first, unconditionally (an unflagged / far
-        // (survivor, part) reads the part's far constant): loads under per-part conditions would be 40 serial round trips
-        unsigned long long wb = 0ull, sel8 = 0ull;
-        int widx[WL_PER], pidx[WL_PER][INVR_NUM_PARTS];
-        float oc[WL_PER][INVR_NUM_PARTS];
-#pragma unroll
-        for (int k = 0; k < WL_PER; ++k)
-#pragma unroll
-            for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-                const bool listed = (fb >> (8 * k + p)) & 1ull;
-                pidx[k][p] = listed ? pos[p] : cidx[p];
-                pos[p] += listed ? 1 : 0;
-            }
-        if (MEAN) {
-            // raws.mean(dim=1) over (Na, P, 4) with zeros for unflagged parts: the per-pair values in part order, / P
-#pragma unroll 2
-            for (int k = 0; k < WL_PER; ++k) {
-                const unsigned fl = (unsigned)(fb >> (8 * k)) & 0xffu, ff = (unsigned)(ffb >> (8 * k)) & 0xffu;
-                float4 v[INVR_NUM_PARTS];
-#pragma unroll
-                for (int p = 0; p < INVR_NUM_PARTS; ++p) v[p] = w.feat[p][(int64_t)pidx[k][p] * 4];      // (unflagged: the part's far constant, dropped below)
-                float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (MODE == 2) {
-                    // torch.sum(raws * F.normalize(1.0 / (part_dist + 1e-5), dim=-1)[..., None], dim=1)
-                    float inv[INVR_NUM_PARTS], n2 = 0.0f;
-                    const int64_t sl = min(s0 + k, (int64_t)na - 1);
-#pragma unroll
-                    for (int p = 0; p < INVR_NUM_PARTS; ++p) { inv[p] = 1.0f / (w.pdist[sl * INVR_NUM_PARTS + p] + 1e-5f); n2 += inv[p] * inv[p]; }
-                    const float den = fmaxf(sqrtf(n2), 1e-12f);
-#pragma unroll
-                    for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-                        const float wp = inv[p] / den;
-                        if ((fl | ff) & (1u << p)) { sum.x += v[p].x * wp; sum.y += v[p].y * wp; sum.z += v[p].z * wp; sum.w += v[p].w * wp; }
-                    }
-                    if (s0 + k < na) {
-                        w.rgbw[s0 + k] = sum;
-                        w.wsel[s0 + k] = ((fl | ff) & 0x1fu) ? (uint8_t)0 : (uint8_t)255;
-                    }
-                    continue;
-                }
-#pragma unroll
-                for (int p = 0; p < INVR_NUM_PARTS; ++p)
-                    if ((fl | ff) & (1u << p)) { sum.x += v[p].x; sum.y += v[p].y; sum.z += v[p].z; sum.w += v[p].w; }
-                const float np = (float)INVR_NUM_PARTS;
-                if (s0 + k < na) {
-                    w.rgbw[s0 + k] = make_float4(sum.x / np, sum.y / np, sum.z / np, sum.w / np);
-                    w.wsel[s0 + k] = ((fl | ff) & 0x1fu) ? (uint8_t)0 : (uint8_t)255;
-                }
-            }
-            continue;
-        }
-#pragma unroll
-        for (int k = 0; k < WL_PER; ++k)
-#pragma unroll
-            for (int p = 0; p < INVR_NUM_PARTS; ++p) oc[k][p] = w.occp[p][pidx[k][p]];
-#pragma unroll
-        for (int k = 0; k < WL_PER; ++k) {
-            const unsigned fl = (unsigned)(fb >> (8 * k)) & 0xffu, ff = (unsigned)(ffb >> (8 * k)) & 0xffu;
-            float best = 0.0f;
-            unsigned bsel = 255u;
-            int bidx = 0;
-            if (MODE == 3) {
-                // part_dist.argmin(dim=1): the first minimum (a NaN, from a part with fewer than 4 vertices, wins as in torch)
-                const int64_t sl = min(s0 + k, (int64_t)na - 1);
-                int bp = 0;
-                float bd = w.pdist[sl * INVR_NUM_PARTS];
-#pragma unroll
-                for (int p = 1; p < INVR_NUM_PARTS; ++p) {
-                    const float d = w.pdist[sl * INVR_NUM_PARTS + p];
-                    if (!(bd != bd) && (d < bd || d != d)) { bd = d; bp = p; }
-                }
-#pragma unroll
-                for (int p = 0; p < INVR_NUM_PARTS; ++p)
-                    if (p == bp) {
-                        if (fl & (1u << p)) bsel = (unsigned)p;
-                        else if (ff & (1u << p)) bsel = 8u + (unsigned)p;
-                        bidx = pidx[k][p];
-                    }
-            } else {
-#pragma unroll
-            for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-                float c = 0.0f;
-                unsigned sel = 255u;
-                if (fl & (1u << p)) { c = oc[k][p]; sel = (unsigned)p; }
-                else if (ff & (1u << p)) { c = oc[k][p]; sel = 8u + (unsigned)p; }
-                if (p == 0 || c > best) { best = c; bsel = sel; bidx = pidx[k][p]; }
-            }
-            }
-            widx[k] = bidx;
-            sel8 |= (unsigned long long)bsel << (8 * k);
-            if (bsel < (unsigned)INVR_NUM_PARTS) wb |= 1ull << (8 * k + bsel);
-        }
-        if (s0 + WL_PER <= na) *reinterpret_cast<unsigned long long*>(w.wsel + s0) = sel8;
-        else for (int k = 0; k < WL_PER; ++k) if (s0 + k < na) w.wsel[s0 + k] = (uint8_t)(sel8 >> (8 * k));
-        // winner ranks, then the lists
-        int wpos[INVR_NUM_PARTS];
-#pragma unroll
-        for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-            const int mine = __popcll(wb & (0x0101010101010101ull << p));
-            const int x = wave_incl_sum_i(mine);
-            wpos[p] = x - mine;
-            if (lane == 63) s_cnt[wv][p] = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-            int q = pbase0[p] + wbase[p] + wpos[p];
-            for (int k = 0; k < WL_BLOCK / 64; ++k) { const int c = s_cnt[k][p]; if (k < wv) q += c; wbase[p] += c; }
-#pragma unroll
-            for (int k = 0; k < WL_PER; ++k)
-                if ((wb >> (8 * k + p)) & 1ull) w.wl[p][q++] = widx[k];
-        }
-        __syncthreads();                 // s_cnt is reused by the next tile
-    }
-    if (!MEAN && threadIdx.x < INVR_NUM_PARTS) {
-        const int p = threadIdx.x;
-        int nw = 0, off = 0, ci = 0;
-#pragma unroll
-        for (int q = 0; q < INVR_NUM_PARTS; ++q) if (q == p) { nw = wbase[q]; off = pbase0[q]; ci = cidx[q]; }
-        if (g == g_last) w.wl[p][off + nw++] = ci;               // the far-constant pair: always evaluated
-        w.wcnt[g * INVR_NUM_PARTS + p] = nw;
-    }
+__global__ __launch_bounds__(MLP_BLOCK, 4) void k_part_occ_all(MlpAllArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[OCC_LDS_FLOATS];
+    int64_t tiles[INVR_NUM_PARTS];
+    for (int p = 0; p < INVR_NUM_PARTS; ++p) tiles[p] = (a.counts[p] + MLP_PAIRS_PER_WG - 1) / MLP_PAIRS_PER_WG;
+    for_my_parts(tiles, [&](int p, int vb, int nb) { occ_part(lds, a.pm[p], a.emb[p], a.counts[p], a.cap, a.occp[p], a.feat[p], vb, nb); });
 }
-
-// cfg.aggr == 'mean': every listed pair (and the far-constant pair that ends a part's list) goes through the colour MLP.
-__global__ __launch_bounds__(256) void k_all_lists(Workspace w) {
-    const int na = w.counters[CNT_ACTIVE];
-    const int g_last = (max(na, 1) - 1) / PAIR_GROUP;
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
-#pragma unroll
-    for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-        const int n = w.counters[CNT_PAIRS + p];
-        for (int64_t i = t; i < n; i += nt) w.wl[p][i] = (int)i;
-    }
-    for (int64_t i = t; i < (int64_t)(g_last + 1) * INVR_NUM_PARTS; i += nt)
-        w.wcnt[i] = w.gcount[i] + (i / INVR_NUM_PARTS == g_last ? 1 : 0);
-}
-
-// Phase 2.  A wave's unit of work is a tile of 32 winners (two 16-pair column blocks) of ONE segment (slot group); tile t of a
-// part -> (segment, offset) through a wave-cooperative cursor: 64 segments per window (lane = segment), tile / pair prefix sums
-// by wave scans, the window advanced as the wave's tile index grows — no per-part scan kernel, no LDS, any number of groups.
-struct SegCursor {
-    int g0, tiles_before, pairs_before;      // window start; tiles / pairs of the segments before it
-    int wc, tl, ti, pe;                      // this lane's segment: winners, tiles, inclusive tile prefix, exclusive pair prefix
-    int win_tiles, win_pairs;
-};
-__device__ __forceinline__ void seg_window(SegCursor& c, const int32_t* __restrict__ wcnt, const int32_t* __restrict__ gcount,
-                                           int part, int g_last, int lane) {
-    const int gi = c.g0 + lane;
-    const bool ok = gi <= g_last;
-    c.wc = ok ? wcnt[(int64_t)gi * INVR_NUM_PARTS + part] : 0;
-    const int gc = ok ? gcount[(int64_t)gi * INVR_NUM_PARTS + part] : 0;
-    c.tl = (c.wc + 31) >> 5;
-    const int x = wave_incl_sum_i(c.tl), y = wave_incl_sum_i(gc);
-    c.ti = x; c.pe = y - gc;
-    c.win_tiles = __shfl(x, 63); c.win_pairs = __shfl(y, 63);
-}
-// -> first tile of the segment that holds tile T, the segment's offset in the lists and its winner count
-__device__ __forceinline__ void seg_locate(SegCursor& c, int T, const int32_t* __restrict__ wcnt, const int32_t* __restrict__ gcount,
-                                           int part, int g_last, int lane, int& seg_tile0, int& sb, int& sn) {
-    while (T >= c.tiles_before + c.win_tiles && c.g0 + 64 <= g_last) {
-        c.tiles_before += c.win_tiles; c.pairs_before += c.win_pairs; c.g0 += 64;
-        seg_window(c, wcnt, gcount, part, g_last, lane);
-    }
-    const unsigned long long m = __ballot(c.tiles_before + c.ti > T);
-    const int L = m ? __ffsll((long long)m) - 1 : 63;
-    seg_tile0 = c.tiles_before + __shfl(c.ti - c.tl, L);
-    sb = c.pairs_before + __shfl(c.pe, L);
-    sn = __shfl(c.wc, L);
-}
-
-struct RgbIn { float eb[EMB_STEPS]; float dv[3]; float4 ft; };
 
 template <int NRGB, bool MEAN>
 __device__ __forceinline__ void rgb_part(float* lds, const MlpAllArgs& a, const int part, const int g_last, const int total_tiles,
@@ -574,7 +332,7 @@ __device__ __forceinline__ void rgb_part(float* lds, const MlpAllArgs& a, const 
     const float* __restrict__ occp = a.occp[part];
     const int32_t* __restrict__ l_slot = a.l_slot[part];
     const int32_t* __restrict__ wl = a.wl[part];
-    const int64_t cap = a.cap;
+    const int64_t lcap = a.cap, cap = lcap - 1;                  // (MlpAllArgs::cap is the list capacity; cap as in Workspace and pair_lists.h)
     const int step = nblocks * (MLP_BLOCK / 64);
     int T = vblock * (MLP_BLOCK / 64) + wv;
     if (T >= total_tiles) return;
@@ -589,71 +347,42 @@ __device__ __forceinline__ void rgb_part(float* lds, const MlpAllArgs& a, const 
         va = ja < sn; vb_ = jb < sn;
         ia = wl[sb + min(ja, sn - 1)]; ib = wl[sb + min(jb, sn - 1)];
     };
-    auto load_in = [&](int pa, int pb, RgbIn& A, RgbIn& B) {
-#pragma unroll
-        for (int s = 0; s < EMB_STEPS; ++s) { A.eb[s] = emb[(int64_t)(4 * s + g) * cap + pa]; B.eb[s] = emb[(int64_t)(4 * s + g) * cap + pb]; }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { A.dv[c] = ds[(int64_t)c * a.stride + pa]; B.dv[c] = ds[(int64_t)c * a.stride + pb]; }
-        A.ft = feat[(int64_t)pa * 4 + g]; B.ft = feat[(int64_t)pb * 4 + g];
+    auto load_in = [&](int pa, int pb, MlpIn (&in)[2]) {
+        load_mlp_in<true>(in, emb, lcap, ds, a.stride, {(int64_t)pa, (int64_t)pb}, g);
+        in[0].ft = feat[(int64_t)pa * 4 + g]; in[1].ft = feat[(int64_t)pb * 4 + g];
     };
     // software pipeline: inputs one tile ahead, pair indices two tiles ahead (a list read and the gathers it feeds are two
     // dependent round trips)
     int ia, ib, n_ia, n_ib, nn_ia = 0, nn_ib = 0;
     bool va, vb, n_va, n_vb, nn_va = false, nn_vb = false;
-    RgbIn inA, inB, nA, nB;
+    MlpIn in[2], nx[2];
     tile_pairs(T, ia, ib, va, vb);
-    load_in(ia, ib, inA, inB);
+    load_in(ia, ib, in);
     n_ia = ia; n_ib = ib; n_va = n_vb = false;
     if (T + step < total_tiles) tile_pairs(T + step, n_ia, n_ib, n_va, n_vb);
     for (; T < total_tiles; T += step) {
-        load_in(n_ia, n_ib, nA, nB);                              // (tile T + step; unused past the last tile)
+        load_in(n_ia, n_ib, nx);                                  // (tile T + step; unused past the last tile)
         nn_ia = n_ia; nn_ib = n_ib; nn_va = nn_vb = false;
         if (T + 2 * step < total_tiles) tile_pairs(T + 2 * step, nn_ia, nn_ib, nn_va, nn_vb);
         const int slotA = l_slot[ia], slotB = l_slot[ib];         // consumed by the stores at the end of the tile
         const float occA = occp[ia], occB = occp[ib];
         MlpCol A, B;
-#pragma unroll
-        for (int s = 0; s < EMB_STEPS; ++s) { A.eb[s] = inA.eb[s]; B.eb[s] = inB.eb[s]; }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { A.dv[c] = inA.dv[c]; B.dv[c] = inB.dv[c]; }
-        A.feat[0] = inA.ft.x; A.feat[1] = inA.ft.y; A.feat[2] = inA.ft.z; A.feat[3] = inA.ft.w;
-        B.feat[0] = inB.ft.x; B.feat[1] = inB.ft.y; B.feat[2] = inB.ft.z; B.feat[3] = inB.ft.w;
+        set_in<true>(A, in[0]); set_in<true>(B, in[1]);
+        A.feat[0] = in[0].ft.x; A.feat[1] = in[0].ft.y; A.feat[2] = in[0].ft.z; A.feat[3] = in[0].ft.w;
+        B.feat[0] = in[1].ft.x; B.feat[1] = in[1].ft.y; B.feat[2] = in[1].ft.z; B.feat[3] = in[1].ft.w;
         A.occ = occA; B.occ = occB;
-        st_rgb_in(A, g, fmul);
-        MLP_FENCE();
-        st_rgb1(lds, lane, g, A); st_rgb_in(B, g, fmul);
-        mlp_interleave<RGB_MFMAS_IN, RGB_V_IN>();
-        MLP_FENCE();
-        st_rgb1(lds, lane, g, B);
-        if (NRGB == 3) st_act_split(A); else st_act(A);
-        mlp_interleave<RGB_MFMAS, RGB_V>();
-        MLP_FENCE();
         float4 rA, rB;
-        if (NRGB == 3) {
-            st_rgb2(lds, lane, g, A); st_act_split(B);
-            mlp_interleave<RGB_MFMAS, RGB_V>();
-            MLP_FENCE();
-            st_rgb2(lds, lane, g, B); st_act(A);
-            mlp_interleave<RGB_MFMAS, 1>();
-            MLP_FENCE();
-            rA = st_head(lds, g, A); st_act(B);
-            MLP_FENCE();
-            rB = st_head(lds, g, B);
-        } else {
-            rA = st_head(lds, g, A); st_act(B);
-            MLP_FENCE();
-            rB = st_head(lds, g, B);
-        }
+        rgb_stages<NRGB, false>(lds, lane, g, fmul, A, B, rA, rB);
         if (g == 0) {
-            if (MEAN) {                                           // 'mean': per pair (k_winner_lists<true> sums them per survivor)
+            if (MEAN) {                                           // 'mean' / 'dist': per pair (k_winner_lists<1 / 2> sums them per survivor)
                 if (va) featw[(int64_t)ia * 4] = rA;
                 if (vb) featw[(int64_t)ib * 4] = rB;
-            } else {
-                if (va) a.rgbw[slotA == (int)(cap - 1) ? cap + part : (int64_t)slotA] = rA;
-                if (vb) a.rgbw[slotB == (int)(cap - 1) ? cap + part : (int64_t)slotB] = rB;
+            } else {                                              // the far-constant pair's result goes behind the per-slot ones
+                if (va) a.rgbw[slotA == (int)far_slot(cap) ? far_result_index(cap, part) : (int64_t)slotA] = rA;
+                if (vb) a.rgbw[slotB == (int)far_slot(cap) ? far_result_index(cap, part) : (int64_t)slotB] = rB;
             }
         }
-        inA = nA; inB = nB;
+        in[0] = nx[0]; in[1] = nx[1];
         ia = n_ia; ib = n_ib; va = n_va; vb = n_vb;
         n_ia = nn_ia; n_ib = nn_ib; n_va = nn_va; n_vb = nn_vb;
     }
@@ -664,15 +393,15 @@ template <bool MEAN>
 __global__ __launch_bounds__(MLP_BLOCK, RGB_WPS) void k_part_rgb_all(MlpAllArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
     __shared__ int s_tot[INVR_NUM_PARTS];
-    const int G = (int)gridDim.x, b = (int)blockIdx.x, lane = threadIdx.x & 63;
-    const int na = a.n_active[0], g_last = (max(na, 1) - 1) / PAIR_GROUP;
+    const int lane = threadIdx.x & 63;
+    const int g_last = last_group(a.n_active[0]);
     if (threadIdx.x < INVR_NUM_PARTS) s_tot[threadIdx.x] = 0;
     __syncthreads();
     {   // winner tiles per part (every workgroup sums the segment counts itself)
         int acc[INVR_NUM_PARTS] = {0, 0, 0, 0, 0};
         for (int q = threadIdx.x; q <= g_last; q += MLP_BLOCK)
 #pragma unroll
-            for (int p = 0; p < INVR_NUM_PARTS; ++p) acc[p] += (a.wcnt[(int64_t)q * INVR_NUM_PARTS + p] + 31) >> 5;
+            for (int p = 0; p < INVR_NUM_PARTS; ++p) acc[p] += (a.wcnt[group_row(q, p)] + 31) >> 5;
 #pragma unroll
         for (int p = 0; p < INVR_NUM_PARTS; ++p) {
             acc[p] = __builtin_amdgcn_readlane(wave_incl_sum_i(acc[p]), 63);
@@ -681,19 +410,15 @@ __global__ __launch_bounds__(MLP_BLOCK, RGB_WPS) void k_part_rgb_all(MlpAllArgs 
     }
     __syncthreads();
     int ntile[INVR_NUM_PARTS];
-    int64_t tiles[INVR_NUM_PARTS], total = 0;          // tile counts weighted by the part's colour-MLP cost per pair (17.5 : 9.3 kFLOP)
+    int64_t tiles[INVR_NUM_PARTS];                     // tile counts weighted by the part's colour-MLP cost per pair (17.5 : 9.3 kFLOP)
     for (int p = 0; p < INVR_NUM_PARTS; ++p) {
         ntile[p] = s_tot[p];
         tiles[p] = (int64_t)((ntile[p] + (MLP_BLOCK / 64) - 1) / (MLP_BLOCK / 64)) * (a.pm[p].rgb.n_linear == 3 ? 15 : 8);
-        total += tiles[p];
     }
-    if (total == 0) return;
-    for (int p = 0; p < INVR_NUM_PARTS; ++p) {
-        int vb, nb;
-        if (!part_range(tiles, total, p, b, G, vb, nb)) continue;
+    for_my_parts(tiles, [&](int p, int vb, int nb) {
         if (a.pm[p].rgb.n_linear == 3) rgb_part<3, MEAN>(lds, a, p, g_last, ntile[p], vb, nb);
         else rgb_part<2, MEAN>(lds, a, p, g_last, ntile[p], vb, nb);
-    }
+    });
 }
 
 bool part_mlp_supported(const PartMlpDev& pm) {
@@ -710,27 +435,18 @@ bool part_mlp_supported(const PartMlpDev& pm) {
 int launch_part_mlp_all(const MlpAllArgs& a, const Workspace& w, hipStream_t st) {
     for (int p = 0; p < INVR_NUM_PARTS; ++p)
         if (!part_mlp_supported(a.pm[p])) return 1;
-    const int64_t per_block = (MLP_BLOCK / 64) * MLP_CB * 16;
-    int64_t tiles = cdiv(a.cap, per_block);
+    int64_t tiles = cdiv(a.cap, (int64_t)MLP_PAIRS_PER_WG);
     unsigned grid_occ = (unsigned)(tiles < 256 * 4 ? (tiles > 0 ? tiles : 1) : 256 * 4);
     unsigned grid_rgb = (unsigned)(tiles < 256 * RGB_WPS ? (tiles > 0 ? tiles : 1) : 256 * RGB_WPS);
     hipLaunchKernelGGL(k_part_occ_all, dim3(grid_occ), dim3(MLP_BLOCK), 0, st, a);
     INVR_LAUNCH_CHECK();
-    if (a.aggr == INVR_AGGR_MEAN || a.aggr == INVR_AGGR_DIST) {
-        int64_t lt = cdiv(a.cap, 256);
-        hipLaunchKernelGGL(k_all_lists, dim3((unsigned)(lt < 1024 ? (lt > 0 ? lt : 1) : 1024)), dim3(256), 0, st, w);
-        INVR_LAUNCH_CHECK();
+    if (a.aggr == INVR_AGGR_MEAN || a.aggr == INVR_AGGR_DIST) {      // the sum flows: colour for every listed pair, then the merge
+        if (launch_all_lists(w, st)) return 1;
         hipLaunchKernelGGL(k_part_rgb_all<true>, dim3(grid_rgb), dim3(MLP_BLOCK), 0, st, a);
         INVR_LAUNCH_CHECK();
-        if (a.aggr == INVR_AGGR_MEAN) hipLaunchKernelGGL(k_winner_lists<1>, dim3((unsigned)w.n_groups), dim3(WL_BLOCK), 0, st, w);
-        else hipLaunchKernelGGL(k_winner_lists<2>, dim3((unsigned)w.n_groups), dim3(WL_BLOCK), 0, st, w);
-        INVR_LAUNCH_CHECK();
-        return 0;
+        return launch_winner_lists(w, a.aggr, st);
     }
-    if (a.aggr == INVR_AGGR_MINDIST) hipLaunchKernelGGL(k_winner_lists<3>, dim3((unsigned)w.n_groups), dim3(WL_BLOCK), 0, st, w);
-    else
-    hipLaunchKernelGGL(k_winner_lists<0>, dim3((unsigned)w.n_groups), dim3(WL_BLOCK), 0, st, w);
-    INVR_LAUNCH_CHECK();
+    if (launch_winner_lists(w, a.aggr, st)) return 1;                // the select flows: the merge, then colour for the winners
     hipLaunchKernelGGL(k_part_rgb_all<false>, dim3(grid_rgb), dim3(MLP_BLOCK), 0, st, a);
     INVR_LAUNCH_CHECK();
     return 0;
@@ -740,8 +456,7 @@ int launch_part_mlp_all(const MlpAllArgs& a, const Workspace& w, hipStream_t st)
 int launch_part_mlp(const PartMlpDev& pm, const float* emb, const float* d_soa, int64_t stride,
                     const int32_t* count, int64_t cap, float4* raw_direct, hipStream_t st) {
     if (!part_mlp_supported(pm)) return 1;
-    const int64_t per_block = (MLP_BLOCK / 64) * MLP_CB * 16;
-    int64_t tiles = cdiv(cap, per_block);
+    int64_t tiles = cdiv(cap, (int64_t)MLP_PAIRS_PER_WG);
     unsigned grid = (unsigned)(tiles < 256 * MLP_WPS ? (tiles > 0 ? tiles : 1) : 256 * MLP_WPS);
     if (pm.rgb.n_linear == 3)
         hipLaunchKernelGGL(k_part_mlp<3>, dim3(grid), dim3(MLP_BLOCK), 0, st, pm, emb, d_soa, stride, count, cap, raw_direct);

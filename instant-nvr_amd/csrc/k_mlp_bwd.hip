@@ -85,11 +85,13 @@ __global__ __launch_bounds__(MLP_BLOCK, 1) void k_part_mlp_bwd(PartMlpDev pm, co
         const bool live = t0 + col < n;
         MP(7)
         // ---------------- forward recompute (k_part_mlp, one column block) ----------------
+        MlpIn in[1];
+        load_mlp_in<true>(in, emb, stride, ds, stride, {pair}, g);
         float eb[EMB_STEPS], dv[3];
 #pragma unroll
-        for (int s = 0; s < EMB_STEPS; ++s) eb[s] = emb[(int64_t)(4 * s + g) * stride + pair];
+        for (int s = 0; s < EMB_STEPS; ++s) eb[s] = in[0].eb[s];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) dv[c] = ds[(int64_t)c * stride + pair];
+        for (int c = 0; c < 3; ++c) dv[c] = in[0].dv[c];
         f32x4 h1[4];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) h1[mt] = bias4(lds + O_B_OCC1, mt, g);

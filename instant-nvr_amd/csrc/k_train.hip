@@ -13,6 +13,7 @@
 // and dense (Na*P, .) scatter tensors per iteration.
 #include <string.h>
 #include "pipeline.h"
+#include "pair_lists.h"
 #include "grid_generic.h"
 #include "deform_mlp.h"
 #include "train.h"
@@ -173,14 +174,8 @@ __global__ __launch_bounds__(256) void k_merge_bwd(Workspace w, const float4* __
             // part's weight normalize(1 / (part_dist + 1e-5)) instead of 1 / P (the weights depend on the geometry alone: no gradient)
             const unsigned fl = w.pflags[slot], ff = w.farflags[slot];
             float wgt[INVR_NUM_PARTS];
-            if (MODE == 2) {
-                float n2 = 0.0f;
-#pragma unroll
-                for (int p = 0; p < INVR_NUM_PARTS; ++p) { wgt[p] = 1.0f / (w.pdist[(int64_t)slot * INVR_NUM_PARTS + p] + 1e-5f); n2 += wgt[p] * wgt[p]; }
-                const float den = fmaxf(sqrtf(n2), 1e-12f);
-#pragma unroll
-                for (int p = 0; p < INVR_NUM_PARTS; ++p) wgt[p] = wgt[p] / den;
-            } else {
+            if (MODE == 2) dist_weights(w.pdist + (int64_t)slot * INVR_NUM_PARTS, wgt);
+            else {
 #pragma unroll
                 for (int p = 0; p < INVR_NUM_PARTS; ++p) wgt[p] = 1.0f / (float)INVR_NUM_PARTS;
             }
@@ -190,21 +185,19 @@ __global__ __launch_bounds__(256) void k_merge_bwd(Workspace w, const float4* __
                 const float4 gp = make_float4(g.x * s, g.y * s, g.z * s, g.w * s);
                 g_raws[(int64_t)slot * INVR_NUM_PARTS + p] = (fl & (1u << p)) ? gp : make_float4(0.f, 0.f, 0.f, 0.f);
                 if (!(fl & (1u << p)) && (ff & (1u << p))) {
-                    float* c = reinterpret_cast<float*>(g_raws + w.cap * INVR_NUM_PARTS + p);
+                    float* c = reinterpret_cast<float*>(g_raws + far_slot(w.cap) * INVR_NUM_PARTS + p);
                     unsafeAtomicAdd(c, gp.x); unsafeAtomicAdd(c + 1, gp.y); unsafeAtomicAdd(c + 2, gp.z); unsafeAtomicAdd(c + 3, gp.w);
                 }
             }
             continue;
         }
-        // the forward's merge (k_winner_lists): p = the listed pair of part p, 8 + p = the far constant of part p, 255 = zeros
+        // the forward's merge (k_winner_lists; the WSEL_ code of pair_lists.h)
         const unsigned sel = w.wsel[slot];
-        const int best_p = sel < 16u ? (int)(sel & 7u) : -1;
-        const bool best_far = sel >= 8u && sel < 16u;
 #pragma unroll
         for (int p = 0; p < INVR_NUM_PARTS; ++p)
-            g_raws[(int64_t)slot * INVR_NUM_PARTS + p] = (p == best_p && !best_far) ? g : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (best_far) {
-            float* c = reinterpret_cast<float*>(g_raws + w.cap * INVR_NUM_PARTS + best_p);
+            g_raws[(int64_t)slot * INVR_NUM_PARTS + p] = sel == wsel_listed(p) ? g : make_float4(0.f, 0.f, 0.f, 0.f);
+        if (wsel_is_far(sel)) {
+            float* c = reinterpret_cast<float*>(g_raws + far_slot(w.cap) * INVR_NUM_PARTS + wsel_far_part(sel));
             unsafeAtomicAdd(c, g.x); unsafeAtomicAdd(c + 1, g.y); unsafeAtomicAdd(c + 2, g.z); unsafeAtomicAdd(c + 3, g.w);
         }
     }

@@ -10,6 +10,27 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define HID 64
 #define EMB_STEPS 5              // 20 / 4
 #define RGB1_STEPS 18            // 72 / 4
+#define MLP_PAIRS_PER_WG ((MLP_BLOCK / 64) * MLP_CB * 16)      // pairs of one workgroup iteration of the forward kernels
+
+// The SoA inputs of one pair as lane group g of its column holds them: k-slots 4 s + g of the (padded) 20-wide embedding
+// (emb[k][pair], rows of `estride`) and, with DIRS, the canonical view direction (ds[c][pair], rows of `dstride`) — for the N
+// column blocks of a wave at once (the forward kernels' two: their loads interleave).  Also the "inputs of the next tile" of the
+// forward kernels' software pipelines (ft: the geometry features, colour phase only).
+struct MlpIn { float eb[EMB_STEPS]; float dv[3]; float4 ft; };
+template <bool DIRS, int N>
+__device__ __forceinline__ void load_mlp_in(MlpIn (&in)[N], const float* __restrict__ emb, int64_t estride, const float* __restrict__ ds,
+                                            int64_t dstride, const int64_t (&pair)[N], int g) {
+#pragma unroll
+    for (int s = 0; s < EMB_STEPS; ++s)
+#pragma unroll
+        for (int j = 0; j < N; ++j) in[j].eb[s] = emb[(int64_t)(4 * s + g) * estride + pair[j]];
+    if (DIRS) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int j = 0; j < N; ++j) in[j].dv[c] = ds[(int64_t)c * dstride + pair[j]];
+    }
+}
 
 // The colour MLP's two 64-wide layers (70 -> 64 and 64 -> 64) in the FORWARD kernels run on the bf16 matrix pipe at fp32 accuracy:
 // weights and activations are split into three bf16 terms (hi + mid + lo = the fp32 value exactly: 3 x 8 significand bits), and the six

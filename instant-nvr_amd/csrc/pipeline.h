@@ -85,8 +85,8 @@ struct Workspace {
     int32_t* wl[INVR_NUM_PARTS];          // cap : winner lists, segmented by slot group: the winners of group g sit at
                                           //       wl[p][pair offset of g ...), wcnt[g][p] of them (pair indices, ascending)
     int32_t* wcnt;                        // [n_groups][INVR_NUM_PARTS]
-    uint8_t* wsel;                        // cap : merge result per survivor: p = listed pair of part p wins, 8 + p = far constant of
-                                          //       part p wins, 255 = zeros (no flagged part, or an unflagged part 0 ties at 0)
+    uint8_t* wsel;                        // cap : merge result per survivor (the WSEL_ code of pair_lists.h): the listed pair of a part
+                                          //       wins, the far constant of a part wins, or zeros
     float4* rgbw;                         // cap + 8 : [rgb, occ] of the winning listed pair per survivor; [lcap + p] = far constant of part p
     uint8_t* cullmask;                    // CULL_MASK_MAX : 1 if the trilinear cell can hold a survivor (k_cull.hip)
     float2* dslice;                       // DF_SLICE_MAX : per-frame t-slices of the deformer grid (k_warp.hip)
@@ -159,6 +159,10 @@ int launch_pose_points(const RenderArgs& a, const int32_t* idx, int64_t n, float
 int launch_knn_voxel_class(const RenderArgs& a, const Workspace& w, hipStream_t st);
 int launch_knn_pairs(const RenderArgs& a, const Workspace& w, int32_t* stats, hipStream_t st);     // stats: exported behind the pair lists when given
 int launch_knn_pdist(const RenderArgs& a, const Workspace& w, hipStream_t st);      // aggr 'dist' / 'mindist': part_dist of all (survivor, part)
+// k_lists.hip (the layout: pair_lists.h).  Launched by launch_knn_pairs (pair lists) and launch_part_mlp_all (winner lists)
+int launch_pair_lists(const Workspace& w, int32_t* stats, hipStream_t st);           // flag bytes -> l_slot, far-constant pairs, counters (-> stats when given)
+int launch_winner_lists(const Workspace& w, int aggr, hipStream_t st);               // the merge of InvrScene::aggr per survivor: wsel, wl / wcnt or the merged rgbw
+int launch_all_lists(const Workspace& w, hipStream_t st);                            // 'mean' / 'dist': every listed pair wins
 int launch_warp_pairs(const RenderArgs& a, const Workspace& w, const GridDev& dg, const MlpDev& dm, hipStream_t st);
 int launch_part_encode(const GridDev& g, const float* x_soa, int64_t stride, const int32_t* count, int64_t cap,
                        float* emb, hipStream_t st);

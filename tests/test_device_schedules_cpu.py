@@ -1,10 +1,10 @@
 """CPU mirrors of two integer schedules the kernels compute from device-side counts (no GPU needed): they pin the arithmetic the
-comments in csrc/k_mlp.hip (k_part_mlp_all: one part per workgroup) and csrc/k_knn.hip (k_pair_lists: list offsets from the
-per-group pair counts) describe, over random and degenerate count vectors."""
+comments in csrc/k_mlp.hip (k_part_mlp_all: one part per workgroup) and csrc/k_lists.hip / csrc/pair_lists.h (k_pair_lists: list
+offsets from the per-group pair counts) describe, over random and degenerate count vectors."""
 import numpy as np
 
 P = 5
-PER_BLOCK = 128          # (MLP_BLOCK / 64) * MLP_CB * 16
+PER_BLOCK = 128          # MLP_PAIRS_PER_WG = (MLP_BLOCK / 64) * MLP_CB * 16
 PAIR_GROUP = 4096
 
 
@@ -53,7 +53,7 @@ def test_every_mlp_tile_is_served_exactly_once():
 
 
 def test_pair_list_offsets_give_ascending_dense_lists():
-    """csrc/k_knn.hip:k_pair_lists — a group's list offset is the sum of the counts of the groups before it; inside a group the
+    """csrc/k_lists.hip:k_pair_lists (group_bases / block_rank5, csrc/pair_lists.h) — a group's list offset is the sum of the counts of the groups before it; inside a group the
     ranks follow the slot order."""
     rng = np.random.default_rng(1)
     for na in (0, 1, 63, 4096, 4097, 300000):
@@ -76,7 +76,7 @@ def test_pair_list_offsets_give_ascending_dense_lists():
             assert np.array_equal(lists[p][:-1], want)            # dense, ascending, every flagged slot once
 
 
-# ---- round 3: the colour kernel's segment cursor (csrc/k_mlp.hip: seg_window / seg_locate / rgb_part) ----------------------------
+# ---- round 3: the colour kernel's segment cursor (csrc/pair_lists.h: seg_window / seg_locate; csrc/k_mlp.hip: rgb_part) ----------------------------
 def rgb_tiles_by_cursor(wcnt, gcount, n_waves):
     """Mirror of k_part_rgb_all for ONE part: the winners of slot group g sit at list positions [pairs before g, + wcnt[g]); a
     wave's unit is a tile of 32 winners of one segment; tile T -> (segment, offset) through a cursor over windows of 64
@@ -131,9 +131,9 @@ def test_colour_kernel_segment_cursor_visits_every_winner_once():
 
 # ---- round 3: the merge rule of k_winner_lists against the oracle's merge (inb_part_network_multiassign.py:229-256) --------------
 def wsel_mirror(occ, listed, far, occ_const):
-    """csrc/k_mlp.hip:k_winner_lists per survivor: candidates = listed occupancy / the part's far constant / 0 for an unflagged part;
+    """csrc/k_lists.hip:k_winner_lists per survivor: candidates = listed occupancy / the part's far constant / 0 for an unflagged part;
     start from part 0 whatever it is, a later part takes over only with a strictly larger occupancy.
-    -> sel: p (listed pair of part p), 8 + p (far constant of part p), 255 (zeros)."""
+    -> sel (the WSEL_ code of csrc/pair_lists.h): p (listed pair of part p), 8 + p (far constant of part p), 255 (zeros)."""
     n = occ.shape[0]
     sel = np.full(n, 255, np.int64)
     best = np.zeros(n, np.float32)

@@ -115,7 +115,7 @@ def test_cull_survivor_set_exact_whole_frame(fr):
 
 
 def check_pairs(f, mins, dfar2=0.4624):
-    """What k_knn_pairs / k_pair_lists left in the workspace of the frame `f` (make_frame's dict; 'S' / 'dev' override the module's
+    """What k_knn_pairs / k_pair_lists (csrc/k_knn.hip, csrc/k_lists.hip) left in the workspace of the frame `f` (make_frame's dict; 'S' / 'dev' override the module's
     sample count / device) against the brute-force stage kernel on the identical pose points, for ALL survivors and all five parts;
     mins = the least counts ('na', 'listed') the frame must reach.  dfar2: the far-fold distance^2 of the frame (None: the one
     part_prepare_body derived, read from the workspace).  -> (nn, d2, w, dist) of invr_knn_neighbors.  (tests/test_gpu_knn_adversarial.py
@@ -361,7 +361,7 @@ def test_render_strict_1e4_on_well_conditioned_pixels(fr):
 
 
 def test_two_phase_mlp_and_winner_lists_vs_whole_field(fr):
-    """The part MLPs run in two phases since round 3 (k_part_occ_all -> k_winner_lists -> k_part_rgb_all: colour only for the pair
+    """The part MLPs run in two phases since round 3 (k_part_occ_all -> k_winner_lists -> k_part_rgb_all, csrc/k_mlp.hip and csrc/k_lists.hip: colour only for the pair
     that wins its survivor's max-occupancy merge).  For the WHOLE frame (2.4 M survivors, 584 slot groups: the colour kernel's
     segment cursor crosses several 64-group windows) at every pose:
       * occp of every listed pair = the occupancy of the one-kernel field evaluation (invr_part_field_fwd: encoder + both MLPs for

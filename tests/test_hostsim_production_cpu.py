@@ -1,15 +1,15 @@
 """CPU: the PRODUCTION kernels of the eval frame (k_knn_pairs, k_warp_pairs + k_deform_pairs, k_part_encode_rs_xcd, k_part_occ_all /
-k_winner_lists / k_part_rgb_all) pinned directly — the test bodies of tests/test_gpu_production_kernels.py on a reduced frame
+k_winner_lists / k_part_rgb_all; the list kernels: csrc/k_lists.hip) pinned directly — the test bodies of tests/test_gpu_production_kernels.py on a reduced frame
 (96 x 96 pixels x 64 samples, 2^12-row tables) through the host build of the kernel sources (tests/hostsim).  The frame is large
 enough for several 4096-slot groups (segmented pair / winner lists, the colour kernel's segment cursor) and for every class of the
 KNN's lattice cells; the whole-frame sizes stay with -m gpu."""
-import copy
 import os
 
 import pytest
 import torch
 
 import tests.test_gpu_production_kernels as P
+from tests.test_gpu_list_groups import make_small_net
 from tests.hostsim import harness
 
 SMALL = dict(RES=96, S=64,
@@ -38,17 +38,7 @@ def hostsim():
 
 @pytest.fixture(scope='module')
 def small_net(hostsim):
-    from invr.config import make_cfg
-    from invr.network import Network
-    torch.manual_seed(11)
-    cfg = make_cfg(table_log2=12, N_samples=SMALL['S'])
-    net = Network(cfg=copy.deepcopy(cfg)).eval()
-    g = torch.Generator().manual_seed(0)
-    with torch.no_grad():
-        for name, p in net.named_parameters():
-            if name.endswith('embedder.dense') or name.endswith('embedder.hash'):
-                p.normal_(0.0, 0.1, generator=g)
-    return cfg, net
+    return make_small_net('cpu', SMALL['S'])
 
 
 @pytest.fixture(scope='module', params=POSE_IDS, ids=['pose%d' % i for i in POSE_IDS])
