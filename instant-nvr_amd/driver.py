@@ -175,6 +175,57 @@ def run_mesh(net, batches, out_dir, level=0.1, voxel_size=None, view_from=None, 
     return out
 
 
+def run_poses(net, scenes, frames, camera, in_flight=None, on_frame=None, renderer=None):
+    """Render a motion the host has only SMPL output for.  scenes: an invr.posescene.PoseScenes; frames: an iterable of keyword dicts
+    for PoseScenes.frame (wxyz, Th, poses, latent_index, R or Rh, ...); camera: (H, W, K, R, T), or a callable of the frame number that
+    returns one (a moving camera).  Frame f's scene tensors are built on the device and its render is submitted (Renderer.render with
+    `in_flight` lanes, chosen as run_evaluate chooses them) while the older frames still render; a frame's tensors are referenced by
+    its batch until it has been joined.  The assembled (H,W,3) host image and (H,W) accumulated opacity go to on_frame(i, img, acc);
+    without on_frame -> the list of (img, acc).  A renderer the caller passes in keeps its lanes (a second motion starts warm) and gets
+    its own in_flight back on return."""
+    from collections import deque
+    net.eval()
+    own = renderer is None
+    renderer = renderer or Renderer(net)
+    prev_in_flight = renderer.in_flight
+    if in_flight is None:
+        cfg_v = getattr(net, 'cfg', {}).get('render_in_flight', None) if hasattr(getattr(net, 'cfg', None), 'get') else None
+        in_flight = int(cfg_v) if cfg_v else 8
+    if scenes.device.type == 'cuda' and torch.cuda.is_available():
+        in_flight = _lanes_that_fit(max(1, int(in_flight)), scenes.device)
+    renderer.in_flight = max(1, int(in_flight))
+    out = []
+    queue = deque()
+
+    def finish(i, ret, batch):
+        rgb = ret['rgb_map'][0].detach().cpu().numpy()              # joins the frame
+        acc = ret['acc_map'][0].detach().cpu().numpy()
+        img = assemble_image(rgb, batch)
+        mask = batch['mask_at_box'][0].detach().cpu().numpy().reshape(img.shape[:2])
+        acc_img = np.zeros(mask.shape, acc.dtype)
+        acc_img[mask] = acc
+        if on_frame is not None:
+            on_frame(i, img, acc_img)
+        else:
+            out.append((img, acc_img))
+
+    try:
+        for i, kw in enumerate(frames):
+            frame = scenes.frame(**kw)
+            batch = scenes.eval_batch(frame, *(camera(i) if callable(camera) else camera))
+            with torch.no_grad():
+                ret = renderer.render(batch)
+            queue.append((i, ret, batch))
+            while len(queue) >= renderer.in_flight:
+                finish(*queue.popleft())
+        while queue:
+            finish(*queue.popleft())
+    finally:
+        renderer.in_flight = prev_in_flight
+        renderer.flush(release=own)
+    return None if on_frame is not None else out
+
+
 _SCALER = None
 
 

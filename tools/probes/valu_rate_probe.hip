@@ -67,6 +67,14 @@ __global__ __launch_bounds__(1024) void k(float* out, long long* cyc, float seed
 #define X(i) asm volatile("v_cmp_le_f32 vcc, %0, %1\n v_cndmask_b32 %0, %0, %1, vcc" : "+v"(f[i]) : "v"(m.x) : "vcc");
                 REP8(X)
 #undef X
+            } else if (KIND == 12) {
+#define X(i) asm volatile("v_mul_f64 %0, %0, %1" : "+v"(d[i]) : "v"(dm));
+                REP8(X)
+#undef X
+            } else if (KIND == 13) {
+#define X(i) asm volatile("v_fma_f64 %0, %0, %1, %1" : "+v"(d[i]) : "v"(dm));
+                REP8(X)
+#undef X
             }
         }
     }
@@ -108,5 +116,7 @@ int main() {
     run<9>("v_mul_lo_u32", out, cyc, 1);
     run<10>("v_exp_f32", out, cyc, 1);
     run<11>("v_cmp_le_f32 + v_cndmask", out, cyc, 2);
+    run<12>("v_mul_f64", out, cyc, 1);
+    run<13>("v_fma_f64", out, cyc, 1);
     return 0;
 }
