@@ -232,6 +232,10 @@ typedef struct InvrWsLayout {
     int64_t byte_off;                      /* int32[ceil(N/1024)*128]: rank of the first survivor of each 8-sample mask byte — written by eval
                                               frames (invr_render_fwd without jitter / weights, power-of-two n_samples in 8..1024), whose
                                               survivors are ranked by depth window inside blocks of 8192 ray-samples       */
+    int64_t dslice;                        /* float2[4096]: per-frame (u, v) slices of the deformer grid at t = frame_dim, level l at entry
+                                              sum_{k<l} res_k^2, entry (cx, cy) = (1 - tz) row(cx, cy, c0z) + tz row(cx, cy, c1z) — written
+                                              when the grid has 8 levels whose slices hold at most 4096 entries, untouched otherwise and
+                                              at and past the last level's end                                                          */
 } InvrWsLayout;
 int invr_workspace_layout(int64_t n_rays, int32_t n_samples, int64_t max_active, InvrWsLayout* out);
 

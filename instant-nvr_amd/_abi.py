@@ -16,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('INVR_LIB_PATH') or os.path.join(HERE, 'libinvr.so')      # (INVR_LIB_PATH: experiment builds)
 
 MAX_LEVELS, MAX_LINEAR, STATS_LEN = 16, 4, 16
+DF_SLICE_MAX = 4096      # csrc/pipeline.h: float2 entries of the deformer's per-frame slice table (InvrWsLayout.dslice)
 _f32p, _f64p, _i32p, _i64p, _u8p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
 
 
@@ -85,7 +86,7 @@ class InvrWsLayout(C.Structure):
                 ('l_x', C.c_int64 * NUM_PARTS), ('l_d', C.c_int64 * NUM_PARTS), ('l_r', C.c_int64 * NUM_PARTS),
                 ('emb', C.c_int64 * NUM_PARTS), ('occp', C.c_int64 * NUM_PARTS), ('wl', C.c_int64 * NUM_PARTS),
                 ('wcnt', C.c_int64), ('wsel', C.c_int64), ('rgbw', C.c_int64), ('n_groups', C.c_int64), ('knn_dfar2', C.c_int64),
-                ('byte_off', C.c_int64)]
+                ('byte_off', C.c_int64), ('dslice', C.c_int64)]
 
 
 class InvrPerceptualLayout(C.Structure):
@@ -305,6 +306,7 @@ def ws_views(ws, n_rays, S, max_active, n_active=None):
          'byte_off': view(lay.byte_off, (n_rays * S + 1023) // 1024 * 128, torch.int32),        # (eval frames: depth-windowed order)
          'pflags': view(lay.pflags, lc, torch.uint8), 'farflags': view(lay.farflags, lc, torch.uint8),
          'knn_dfar2': view(lay.knn_dfar2, 1, torch.float32),
+         'dslice': view(lay.dslice, DF_SLICE_MAX * 2, torch.float32).view(DF_SLICE_MAX, 2),     # per-frame (u, v) slices of the deformer grid
          'wsel': view(lay.wsel, lc, torch.uint8),                   # merge result per survivor (p / 8 + p / 255)
          'rgbw': view(lay.rgbw, (lc + 8) * 4, torch.float32).view(lc + 8, 4),      # winner's [rgb, occ] per slot; far constants at lc + p
          'wcnt': view(lay.wcnt, lay.n_groups * NUM_PARTS, torch.int32).view(lay.n_groups, NUM_PARTS)}

@@ -411,17 +411,21 @@ __device__ __forceinline__ void deform_slice_body(const GridDev& dg, const DfSli
     int l = 0;
     while (e >= si.off[l + 1]) ++l;
     const int res = dg.res[l];
-    const float tn = grid_norm(dg, 2, frame_dim[0]);
-    int c0z, c1z;
-    float tz;
-    level_corners(tn, dg.cell[l], res, c0z, c1z, tz);
+    // The t-offset in double, rounded ONCE.  level_corners' fp32 quotient f = fl(t_n / cell) is off by half an ulp of f, 2^-24 f
+    // absolute, and tz = f - c0z inherits it whole: up to f / tz half-ulps of tz (234 at f = 7.03), and at frame_dim = 1 the other
+    // side of the last cell's edge.  A point's own (u, v) carry that uncertainty anyway; here it would be baked into every entry of
+    // a table all pairs of the frame read.  One quotient per entry and frame: free.  (Same clip as level_corners_of.)
+    const double b0 = (double)dg.bounds[2], tn = ((double)frame_dim[0] - b0) / ((double)dg.bounds[5] - b0);
+    const double f = tn / (double)dg.cell[l];
+    const int c0z = min(max((int)f, 0), res - 1), c1z = min(max((int)(f + 1.0), 0), res - 1);
+    const double td = f - (double)c0z;
+    const float tz = (float)td, uz = (float)(1.0 - td);
     const int idx = e - si.off[l], cx = idx / res, cy = idx - cx * res;
     const bool hashed = l >= dg.start_hash;
     const float2* tab = reinterpret_cast<const float2*>(grid_level_table<2>(dg, l, hashed));
     const GridRowPair r = grid_row_zpair(dg, hashed, res, c0z, c1z, cx, cy);
     const unsigned r0 = r.r0, r1 = r.r1;
     const float2 v0 = tab[r0], v1 = tab[r1];
-    const float uz = 1.0f - tz;
     out[e] = make_float2(fmaf(tz, v1.x, uz * v0.x), fmaf(tz, v1.y, uz * v0.y));
 }
 

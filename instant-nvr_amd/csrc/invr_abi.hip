@@ -316,6 +316,7 @@ extern "C" int invr_workspace_layout(int64_t n_rays, int32_t n_samples, int64_t 
     for (int p = 0; p < INVR_NUM_PARTS; ++p) o->emb[p] = off(w.emb[p]);
     for (int p = 0; p < INVR_NUM_PARTS; ++p) { o->occp[p] = off(w.occp[p]); o->wl[p] = off(w.wl[p]); }
     o->wcnt = off(w.wcnt); o->wsel = off(w.wsel); o->rgbw = off(w.rgbw); o->n_groups = w.n_groups;
+    o->dslice = off(w.dslice);
     return 0;
 }
 

@@ -327,9 +327,48 @@ def reference(pts, g_resd, P, scene, spec, trials=4, seed=0, on_chunk=None, chun
     return entries, (acc, pnoise, po32, touched)
 
 
-def accept(tag, name, val, ref, noise, o32=None, touched=None):
-    """EC.accept, unchanged: the rule, the NaN / shape checks, the exact zeros, and the K_kernel / K_oracle32 line (prefix DFB)."""
-    return EC.accept(tag, name, val, ref, noise, o32, touched, report=lambda s: print('DFB ' + s[4:]))
+def reference_fwd(pts, P, scene, spec, seed=0, chunk=CHUNK):
+    """reference() for the forward alone: the `resd` entry of reference(pts, zeros, P, scene, spec, seed=seed) — the same float64
+    statements (DR.deformer without its backward), the same fp32 oracle (O.deformer itself, which oracle_chunk asserts its restatement
+    against) and the same draws of the noise classes (b) and (c) in the same order (tests/test_deform_reference_cpu.py holds the
+    two against each other bit for bit) — without the backward, the table scatters and the autograd.
+    -> list of (slice, Ref, noise, o32, z) per chunk, z = the float64 pre-activations {'z1', 'z2', 'z3'} of the chunk."""
+    n = pts.shape[0]
+    g = torch.Generator().manual_seed(3000 + seed)
+    sign = lambda *s: torch.randint(0, 2, s, generator=g).double() * 2.0 - 1.0
+    sd32 = {k: v.detach() for k, v in oracle_sd(P, spec, torch.float32).items()}
+    s32 = {k: scene[k].float() for k in ('tuv', 'tbounds', 'frame_dim')}
+    s64 = {k: scene[k].double() for k in ('tuv', 'tbounds', 'frame_dim')}           # (converted once, not per evaluation: large volumes)
+    zeros = torch.zeros(0, 3)
+    out = []
+    for lo in range(0, max(n, 1), chunk):
+        sl = slice(lo, min(lo + chunk, n))
+        x = pts[sl]
+        m = x.shape[0]
+        r = DR.deformer(x, zeros, P, s64, spec, backward=False)
+        with torch.no_grad():
+            o32 = torch.cat([O.deformer(x[i:i + 8192].float(), sd32, spec, s32['tuv'], s32['tbounds'], s32['frame_dim'])
+                             for i in range(0, m, 8192)], 0) if m else torch.zeros(0, 3)
+        noise = (o32.double() - r['resd'].exact).abs()
+        x64 = x.double()
+        order = torch.rand(m, 4, generator=g).argsort(1)
+        for t in range(8):
+            if t < 4:                                                                                            # (b)
+                sx = _PATTERNS[order[:, t]] * sign(m, 1)
+                sign(m, 3)                                                                                       # (g_resd's draw)
+                p = DR.deformer(x64 + sx * (x64.abs() + 1.0) * 2.0 ** -23, zeros, P, s64, spec, companions=False, backward=False)
+            else:                                                                                                # (c)
+                p = DR.deformer(x64, zeros, P, s64, spec, companions=False, softplus_sign=dict(h1=sign(m, 32), h2=sign(m, 32)),
+                                geometry=r['geometry'], backward=False)
+            noise = torch.maximum(noise, (p['resd'].exact - r['resd'].exact).abs())
+        out.append((sl, r['resd'], noise, o32, r['z']))
+    return out
+
+
+def accept(tag, name, val, ref, noise, o32=None, touched=None, prefix='DFB'):
+    """EC.accept, unchanged: the rule, the NaN / shape checks, the exact zeros, and the K_kernel / K_oracle32 line (prefix DFB; DFF for
+    the forward tests)."""
+    return EC.accept(tag, name, val, ref, noise, o32, touched, report=lambda s: print(prefix + ' ' + s[4:]))
 
 
 preloaded = MC.preloaded

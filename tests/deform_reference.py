@@ -89,11 +89,12 @@ def grid_backward(geo, gfeat, Agf, dense, hsh, spec):
     return {'g_dense': table(0, dr, (dr, F)), 'g_hash': table(dr, R, tuple(hsh.shape))}
 
 
-def deformer(pts, g_resd, P, scene, spec, companions=True, softplus_sign=None, geometry=None):
+def deformer(pts, g_resd, P, scene, spec, companions=True, softplus_sign=None, geometry=None, backward=True):
     """pts, g_resd (n,3) -> dict of Ref (companions False: A = c = None everywhere).  geometry: the 'geometry' entry of an earlier
     result for the same pts (the UV sample and the grid's corner rows / weights are not formed again).  softplus_sign (dict 'h1', 'h2' -> +-1 tensors
     (n,32)): the value-only perturbation of tests/deform_cases.py, noise class (c) — each forward Softplus output moved by that sign
-    times max(1 fp32 ulp of itself, 1.5e-7); the derivative factors stay computed from z."""
+    times max(1 fp32 ulp of itself, 1.5e-7); the derivative factors stay computed from z.  backward False: the forward entries alone
+    (resd, uvt, a0, a1, a2, z, geometry — the same statements; g_resd is not read)."""
     comp = companions
     d = lambda t: t.detach().double()
     W, b = [d(w) for w in P['W']], [d(x) for x in P['b']]
@@ -134,6 +135,14 @@ def deformer(pts, g_resd, P, scene, spec, companions=True, softplus_sign=None, g
     th = torch.tanh(z3)
     sech2 = 1.0 / torch.cosh(z3) ** 2
     resd = 0.05 * th
+    fwd = dict(resd=Ref(resd, (0.05 * (sech2 * Az3 + th.abs())) if comp else None, 35.0),
+               uvt=Ref(uvt, A_uvt, 12.0),
+               a0=Ref(feat, A_feat, 12.0),
+               a1=Ref(h1, (dsoftplus(z1) * Az1 + h1.abs()) if comp else None, 21.0),
+               a2=Ref(h2, (dsoftplus(z2) * Az2 + h2.abs()) if comp else None, 34.0),
+               z=dict(z1=z1, z2=z2, z3=z3), geometry=(uvt, A_uvt, geo))
+    if not backward:
+        return fwd
     # ---- backward ----------------------------------------------------------------------------------------------------------------
     # a derivative factor is itself computed from a pre-activation that fp32 forms as a sum: its companion follows the forward rule
     # A(f(z)) = |f'(z)| A(z) + |f(z)| with f the factor (sigmoid' = sigmoid(z) sigmoid(-z), (1 / cosh^2)' = -2 tanh / cosh^2)
@@ -144,14 +153,7 @@ def deformer(pts, g_resd, P, scene, spec, companions=True, softplus_sign=None, g
     gz2, A2 = mul(*mm(gz3, A3, W[2]), *fac(z2, Az2))
     gz1, A1 = mul(*mm(gz2, A2, W[1]), *fac(z1, Az1))
     gfeat, Agf = mm(gz1, A1, W[0])
-    out = dict(
-        resd=Ref(resd, (0.05 * (sech2 * Az3 + th.abs())) if comp else None, 35.0),
-        uvt=Ref(uvt, A_uvt, 12.0),
-        a0=Ref(feat, A_feat, 12.0),
-        a1=Ref(h1, (dsoftplus(z1) * Az1 + h1.abs()) if comp else None, 21.0),
-        a2=Ref(h2, (dsoftplus(z2) * Az2 + h2.abs()) if comp else None, 34.0),
-        gz3=Ref(gz3, A3, C_GZ3), gz2=Ref(gz2, A2, C_GZ2), gz1=Ref(gz1, A1, C_GZ1), gfeat=Ref(gfeat, Agf, C_GFEAT),
-        z=dict(z1=z1, z2=z2, z3=z3), geometry=(uvt, A_uvt, geo))
+    out = dict(fwd, gz3=Ref(gz3, A3, C_GZ3), gz2=Ref(gz2, A2, C_GZ2), gz1=Ref(gz1, A1, C_GZ1), gfeat=Ref(gfeat, Agf, C_GFEAT))
     nn = float(n) if comp else None
     for l, (gz, Ag, ain) in enumerate(((gz1, A1, feat), (gz2, A2, h1), (gz3, A3, h2))):
         out['dW%d' % l] = Ref(gz.t() @ ain, (Ag.t() @ ain.abs()) if comp else None, nn)

@@ -150,6 +150,49 @@ def test_struct_sizes_match_header():
         assert L.invr_sizeof(i) == C.sizeof(t), t
 
 
+def test_workspace_layout_fields_match_header():
+    """InvrWsLayout, field by field: the binding lists the header's fields in the header's order (all int64_t, arrays of INVR_NUM_PARTS),
+    `dslice` last, after `byte_off`; the library fills every offset inside the workspace, 256-byte aligned, the slice table DF_SLICE_MAX
+    float2 entries long and overlapping no other exported array."""
+    import ctypes as C
+    from invr import _abi
+    src = open(os.path.join(ROOT, 'include', 'invr.h')).read()
+    body = re.search(r'typedef struct InvrWsLayout \{(.*?)\} InvrWsLayout;', src, flags=re.S).group(1)
+    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
+    fields = []
+    for decl in body.split(';'):
+        decl = decl.strip()
+        if decl:
+            assert decl.startswith('int64_t '), decl
+            for name in decl[len('int64_t '):].split(','):
+                m = re.fullmatch(r'\s*([a-z_0-9]+)(\[INVR_NUM_PARTS\])?\s*', name)
+                fields.append((m.group(1), C.c_int64 * _abi.NUM_PARTS if m.group(2) else C.c_int64))
+    assert [(n, t) for n, t in _abi.InvrWsLayout._fields_] == fields
+    assert [n for n, _ in fields][-2:] == ['byte_off', 'dslice']
+    pipeline = open(os.path.join(_abi.HERE, 'csrc', 'pipeline.h')).read()
+    assert int(re.search(r'#define DF_SLICE_MAX (\d+)', pipeline).group(1)) == _abi.DF_SLICE_MAX == 4096
+    L = _abi.lib()
+    for n_rays, S, cap in ((1, 1, 0), (1600, 32, 0), (4096, 64, 1000)):
+        lay = _abi.InvrWsLayout()
+        for n, _ in fields:                                         # (a field the library does not fill keeps this)
+            setattr(lay, n, (C.c_int64 * _abi.NUM_PARTS)(*[-1] * _abi.NUM_PARTS) if n in ('l_slot', 'l_nn', 'l_w', 'l_x', 'l_d', 'l_r', 'emb',
+                                                                                           'occp', 'wl') else -1)
+        assert L.invr_workspace_layout(n_rays, S, cap, C.byref(lay)) == 0
+        total = L.invr_workspace_bytes(n_rays, S, cap)
+        offs = []
+        for n, t in fields:
+            if n in ('cap', 'lcap', 'n_groups'):
+                assert getattr(lay, n) > 0, n
+                continue
+            vals = list(getattr(lay, n)) if t is not C.c_int64 else [getattr(lay, n)]
+            for v in vals:
+                assert 0 <= v < total and v % 256 == 0, (n, v, total)
+            offs += vals
+        assert len(set(offs)) == len(offs)
+        nxt = min(o for o in offs + [total] if o > lay.dslice)
+        assert lay.dslice + _abi.DF_SLICE_MAX * 8 <= nxt <= total, (lay.dslice, nxt, total)
+
+
 def test_product_path_has_no_cpu_route():
     """The render path is the HIP library or nothing: the binding refuses host tensors, and nothing in the product tree, bench.py or
     __graft_entry__.py knows about the test-only host build of the kernels (tests/hostsim) or imports the oracle outside bench.py's

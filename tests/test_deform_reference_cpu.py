@@ -49,6 +49,26 @@ def test_companions_off_and_chunks_give_the_same_values():
         assert ((e1[1][k].exact - cat).abs() <= 1e-13 * e1[1][k].A).all(), k
 
 
+@pytest.mark.parametrize('wtag,cloud,frame', [('wide', 'inside', 'tmid'), ('saturated-head', 'nodes', 't1'), ('init', 'outside', 't0')])
+def test_forward_only_reference_is_the_full_reference(wtag, cloud, frame):
+    """DC.reference_fwd (the forward tests' reference) against the `resd` entry of DC.reference with a zero upstream gradient: exact, A,
+    c, the fp32 oracle and the noise bit for bit, in one chunk and in three."""
+    n = 100
+    spec, P, scene = DC.make_spec('prod'), DC.make_params(wtag), DC.make_scene('prod', frame)
+    pts = DC.make_cloud(cloud, n, 'prod', frame)
+    for chunk in (DC.CHUNK, 37):
+        full, _ = DC.reference(pts, torch.zeros(n, 3), P, scene, spec, chunk=chunk)
+        fwd = DC.reference_fwd(pts, P, scene, spec, chunk=chunk)
+        assert len(full) == len(fwd) == (1 if chunk > n else 3)
+        for (sl, ref, noise, o32), (sl2, r2, n2, o2, z) in zip(full, fwd):
+            assert sl == sl2 and ref['resd'].c == r2.c == 35.0
+            assert torch.equal(ref['resd'].exact, r2.exact) and torch.equal(ref['resd'].A, r2.A)
+            assert torch.equal(o32['resd'], o2) and torch.equal(noise['resd'], n2)
+            assert set(z) == {'z1', 'z2', 'z3'} and z['z3'].shape == (sl.stop - sl.start, 3)
+            assert torch.equal(r2.exact, 0.05 * torch.tanh(z['z3']))
+    assert DC.reference_fwd(torch.zeros(0, 3), P, scene, spec)[0][1].exact.shape == (0, 3)
+
+
 def test_weight_sets_reach_their_ranges():
     for wtag in ('wide', 'saturated-head'):
         for n in (1000, DC.N_BASE):
