@@ -236,6 +236,11 @@ typedef struct InvrWsLayout {
                                               sum_{k<l} res_k^2, entry (cx, cy) = (1 - tz) row(cx, cy, c0z) + tz row(cx, cy, c1z) — written
                                               when the grid has 8 levels whose slices hold at most 4096 entries, untouched otherwise and
                                               at and past the last level's end                                                          */
+    int64_t pdist;                         /* float[lcap*5], [slot][p]: the KNN's part_dist of EVERY (survivor, part) — written for aggr 'dist' and
+                                              'mindist' only (what the merge weights / selects by)                                      */
+    int64_t feat[INVR_NUM_PARTS];          /* float4[lcap*4] per part: scratch of the colour MLP.  After an aggr 'mean' / 'dist' frame entry
+                                              [pair*4] holds the [rgb, occ] of list entry `pair` (the last one = the part's far constant)  */
+    int64_t gcount;                        /* int32[n_groups*5]: listed pairs of part p among the survivors of slot group g, [g][p]     */
 } InvrWsLayout;
 int invr_workspace_layout(int64_t n_rays, int32_t n_samples, int64_t max_active, InvrWsLayout* out);
 
@@ -546,6 +551,17 @@ int invr_train_loss_fwd(const float* rgb_map, const float* rgb_gt, const float* 
                         float w_pair, float w_dist, float w_off, int32_t use_pair, float* out8, float* err, void* stream);
 int invr_train_loss_bwd(const float* rgb_map, const float* rgb_gt, const float* terms, int64_t n_rays, float w_pair, float w_dist,
                         float w_off, int32_t use_pair, const float* g_loss, float* g_rgb, float* g_dist, float* g_terms, void* stream);
+
+/* The merge's transpose alone (stage entry point: the last step of invr_train_bwd's HEAD stage; autograd of
+ * inb_part_network_multiassign.py:229-256 + the scatter of :156-159) on the workspace a forward call (invr_render_fwd or invr_train_fwd)
+ * of the SAME n_rays, n_samples and max_active left: it reads counters, active_idx and — aggr '' / 'mindist' —
+ * wsel, — 'mean' / 'dist' — pflags, farflags (and pdist for 'dist'); aggr as InvrScene::aggr.  g_rawfull (n_rays*n_samples,4): the
+ * gradient w.r.t. the scattered raw.  g_raws (lcap*5,4), lcap = max_active + 1 as InvrWsLayout::lcap: row slot*5 + p = the gradient
+ * w.r.t. the [rgb, occ] of (survivor slot, part p) — every row of the Na survivors is WRITTEN (+0.0 where the pair is not listed or
+ * did not take part); row cap*5 + p = the sum over the far pairs of part p, ACCUMULATED with atomic float adds into a row that the
+ * call itself clears first on `stream`: the caller clears nothing.  The rows of slots [Na, cap) are not touched. */
+int invr_merge_bwd(int32_t aggr, void* workspace, size_t workspace_bytes, int64_t n_rays, int32_t n_samples, int64_t max_active,
+                   const float* g_rawfull, float* g_raws, void* stream);
 
 /* Backward of invr_composite_fwd: g_rgb_map (n_rays,3), g_acc_map (n_rays) or NULL, g_weights
  * (n_rays,n_samples) or NULL (e.g. from the distortion regulariser) -> g_raw (n_rays,n_samples,4). */

@@ -86,7 +86,8 @@ class InvrWsLayout(C.Structure):
                 ('l_x', C.c_int64 * NUM_PARTS), ('l_d', C.c_int64 * NUM_PARTS), ('l_r', C.c_int64 * NUM_PARTS),
                 ('emb', C.c_int64 * NUM_PARTS), ('occp', C.c_int64 * NUM_PARTS), ('wl', C.c_int64 * NUM_PARTS),
                 ('wcnt', C.c_int64), ('wsel', C.c_int64), ('rgbw', C.c_int64), ('n_groups', C.c_int64), ('knn_dfar2', C.c_int64),
-                ('byte_off', C.c_int64), ('dslice', C.c_int64)]
+                ('byte_off', C.c_int64), ('dslice', C.c_int64), ('pdist', C.c_int64), ('feat', C.c_int64 * NUM_PARTS),
+                ('gcount', C.c_int64)]
 
 
 class InvrPerceptualLayout(C.Structure):
@@ -160,6 +161,7 @@ def _signatures():
         'invr_distortion_bwd': (C.c_int, [vp, vp, vp, i64, i32, vp, vp]),
         'invr_train_loss_fwd': (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, i32, vp, vp, vp]),
         'invr_train_loss_bwd': (C.c_int, [vp, vp, vp, i64, f32, f32, f32, i32, vp, vp, vp, vp, vp]),
+        'invr_merge_bwd': (C.c_int, [i32, vp, size, i64, i32, i64, vp, vp, vp]),
         'invr_composite_bwd': (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp]),
         'invr_eval_workspace_bytes': (size, [i32, i32]),
         'invr_image_assemble': (C.c_int, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, size, vp]),
@@ -310,6 +312,9 @@ def ws_views(ws, n_rays, S, max_active, n_active=None):
          'wsel': view(lay.wsel, lc, torch.uint8),                   # merge result per survivor (p / 8 + p / 255)
          'rgbw': view(lay.rgbw, (lc + 8) * 4, torch.float32).view(lc + 8, 4),      # winner's [rgb, occ] per slot; far constants at lc + p
          'wcnt': view(lay.wcnt, lay.n_groups * NUM_PARTS, torch.int32).view(lay.n_groups, NUM_PARTS)}
+    v['pdist'] = view(lay.pdist, lc * NUM_PARTS, torch.float32).view(lc, NUM_PARTS)      # part_dist per (slot, part): aggr 'dist' / 'mindist' frames
+    v['gcount'] = view(lay.gcount, lay.n_groups * NUM_PARTS, torch.int32).view(lay.n_groups, NUM_PARTS)
+    v['feat'] = [view(lay.feat[p], lc * 16, torch.float32).view(lc * 4, 4) for p in range(NUM_PARTS)]      # 'mean' / 'dist': row pair * 4 = the pair's [rgb, occ]
     v['occp'] = [view(lay.occp[p], lc, torch.float32) for p in range(NUM_PARTS)]      # occupancy of every listed pair
     v['wl'] = [view(lay.wl[p], lc, torch.int32) for p in range(NUM_PARTS)]
     for k in ('l_slot', 'l_x', 'l_d', 'l_r'):

@@ -317,6 +317,8 @@ extern "C" int invr_workspace_layout(int64_t n_rays, int32_t n_samples, int64_t 
     for (int p = 0; p < INVR_NUM_PARTS; ++p) { o->occp[p] = off(w.occp[p]); o->wl[p] = off(w.wl[p]); }
     o->wcnt = off(w.wcnt); o->wsel = off(w.wsel); o->rgbw = off(w.rgbw); o->n_groups = w.n_groups;
     o->dslice = off(w.dslice);
+    o->pdist = off(w.pdist); o->gcount = off(w.gcount);
+    for (int p = 0; p < INVR_NUM_PARTS; ++p) o->feat[p] = off(w.feat[p]);
     return 0;
 }
 
@@ -991,6 +993,23 @@ extern "C" int invr_train_fwd(const InvrScene* scene, const InvrModel* model,
         INVR_LAUNCH_CHECK();
     }
     return 0;
+}
+
+// The merge's transpose alone, on the workspace a forward call of the same sizes left (stage entry point: what
+// tests/test_gpu_merge_modes.py holds survivor by survivor to the reference's merge)
+extern "C" int invr_merge_bwd(int32_t aggr, void* workspace, size_t workspace_bytes, int64_t n_rays, int32_t n_samples, int64_t max_active,
+                              const float* g_rawfull, float* g_raws, void* stream) {
+    INVR_CHECK(aggr >= INVR_AGGR_MAX && aggr <= INVR_AGGR_MINDIST, "invr_merge_bwd: aggr %d (0 = max-occupancy merge, 1 = mean, 2 = dist, 3 = mindist)", aggr);
+    INVR_CHECK(n_rays >= 0 && n_samples >= 1, "invr_merge_bwd: need n_rays >= 0 and n_samples >= 1");
+    if (n_rays == 0) return 0;
+    const int64_t N = n_rays * (int64_t)n_samples;
+    INVR_CHECK(N < (1ll << 31), "invr_merge_bwd: n_rays*n_samples must be < 2^31 (got %lld)", (long long)N);
+    INVR_CHECK(g_rawfull && g_raws, "invr_merge_bwd: null g_rawfull / g_raws");
+    Workspace w;
+    const size_t need = carve(w, workspace, N, clamp_active(N, max_active));
+    INVR_CHECK(workspace != nullptr && workspace_bytes >= need, "invr_merge_bwd: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    INVR_CHECK(((uintptr_t)workspace & 255) == 0, "invr_merge_bwd: workspace must be 256-byte aligned");
+    return launch_merge_bwd(w, aggr, reinterpret_cast<const float4*>(g_rawfull), reinterpret_cast<float4*>(g_raws), (hipStream_t)stream);
 }
 
 __global__ void k_part_active(const int32_t* __restrict__ counters, float* __restrict__ act) {

@@ -60,7 +60,7 @@ def test_library_exports_header_symbols():
     assert int(re.search(r'#define INVR_ABI_VERSION (\d+)', hdr).group(1)) == _abi.ABI_VERSION
     # every declaration parses as a prototype, and the binding's one table states each with the header's types, in the header's order
     protos = header_prototypes()
-    assert len(protos) == 53
+    assert len(protos) == 54
     assert sorted(name for _, name, _ in protos) == names, 'an invr_ declaration of the header did not parse as a prototype'
     assert [name for _, name, _ in protos] == list(_abi.SIGNATURES) == _abi.EXPORTS
     for ret, name, params in protos:
@@ -135,6 +135,29 @@ def test_workspace_query_and_error_path():
     assert st != 0
 
 
+def test_merge_bwd_argument_checks():
+    """invr_merge_bwd stops at its argument checks (nothing is launched): the merge mode, the sizes, the pointers, the workspace's size
+    and alignment."""
+    import ctypes as C
+    from invr import _abi
+    L = _abi.lib()
+    need = L.invr_workspace_bytes(64, 8, 0)
+    buf = C.create_string_buffer(512)
+    base = (C.addressof(buf) + 255) & ~255
+    g = C.cast(buf, C.c_void_p)
+    for args, msg in (((4, base, need, 64, 8, 0, g, g, None), b'aggr 4'),
+                      ((-1, base, need, 64, 8, 0, g, g, None), b'aggr -1'),
+                      ((1, base, need, 64, 0, 0, g, g, None), b'n_samples >= 1'),
+                      ((1, base, need, 1 << 26, 64, 0, g, g, None), b'< 2^31'),
+                      ((1, base, need, 64, 8, 0, None, g, None), b'null g_rawfull'),
+                      ((1, base, need, 64, 8, 0, g, None, None), b'null g_rawfull'),
+                      ((1, None, need, 64, 8, 0, g, g, None), b'workspace too small'),
+                      ((1, base, need - 1, 64, 8, 0, g, g, None), b'workspace too small'),
+                      ((1, base + 16, need, 64, 8, 0, g, g, None), b'256-byte aligned')):
+        assert L.invr_merge_bwd(*args) != 0 and msg in L.invr_last_error(), (args, L.invr_last_error())
+    assert L.invr_merge_bwd(1, None, 0, 0, 8, 0, None, None, None) == 0          # no rays: nothing to do
+
+
 def test_struct_sizes_match_header():
     """ctypes mirrors must have the C layout (checked against sizes computed from the header's field lists)."""
     import ctypes as C
@@ -152,8 +175,10 @@ def test_struct_sizes_match_header():
 
 def test_workspace_layout_fields_match_header():
     """InvrWsLayout, field by field: the binding lists the header's fields in the header's order (all int64_t, arrays of INVR_NUM_PARTS),
-    `dslice` last, after `byte_off`; the library fills every offset inside the workspace, 256-byte aligned, the slice table DF_SLICE_MAX
-    float2 entries long and overlapping no other exported array."""
+    `dslice` after `byte_off`, then the merge's inputs `pdist`, `feat`, `gcount` — appended, so that no older field moved; the library
+    fills every offset inside the workspace, 256-byte aligned (gcount: behind the 16 counters, 64-byte aligned), the slice table
+    DF_SLICE_MAX float2 entries long and overlapping no other exported array, pdist / feat / gcount with room for their documented
+    lengths before the next exported array."""
     import ctypes as C
     from invr import _abi
     src = open(os.path.join(ROOT, 'include', 'invr.h')).read()
@@ -168,15 +193,16 @@ def test_workspace_layout_fields_match_header():
                 m = re.fullmatch(r'\s*([a-z_0-9]+)(\[INVR_NUM_PARTS\])?\s*', name)
                 fields.append((m.group(1), C.c_int64 * _abi.NUM_PARTS if m.group(2) else C.c_int64))
     assert [(n, t) for n, t in _abi.InvrWsLayout._fields_] == fields
-    assert [n for n, _ in fields][-2:] == ['byte_off', 'dslice']
+    assert [n for n, _ in fields][-5:] == ['byte_off', 'dslice', 'pdist', 'feat', 'gcount']
+    arrays5 = ('l_slot', 'l_nn', 'l_w', 'l_x', 'l_d', 'l_r', 'emb', 'occp', 'wl', 'feat')
+    assert [n for n, t in fields if t is not C.c_int64] == list(arrays5)
     pipeline = open(os.path.join(_abi.HERE, 'csrc', 'pipeline.h')).read()
     assert int(re.search(r'#define DF_SLICE_MAX (\d+)', pipeline).group(1)) == _abi.DF_SLICE_MAX == 4096
     L = _abi.lib()
     for n_rays, S, cap in ((1, 1, 0), (1600, 32, 0), (4096, 64, 1000)):
         lay = _abi.InvrWsLayout()
         for n, _ in fields:                                         # (a field the library does not fill keeps this)
-            setattr(lay, n, (C.c_int64 * _abi.NUM_PARTS)(*[-1] * _abi.NUM_PARTS) if n in ('l_slot', 'l_nn', 'l_w', 'l_x', 'l_d', 'l_r', 'emb',
-                                                                                           'occp', 'wl') else -1)
+            setattr(lay, n, (C.c_int64 * _abi.NUM_PARTS)(*[-1] * _abi.NUM_PARTS) if n in arrays5 else -1)
         assert L.invr_workspace_layout(n_rays, S, cap, C.byref(lay)) == 0
         total = L.invr_workspace_bytes(n_rays, S, cap)
         offs = []
@@ -186,11 +212,20 @@ def test_workspace_layout_fields_match_header():
                 continue
             vals = list(getattr(lay, n)) if t is not C.c_int64 else [getattr(lay, n)]
             for v in vals:
-                assert 0 <= v < total and v % 256 == 0, (n, v, total)
+                # (gcount shares the counters' allocation — one memset clears both: it follows them inside it)
+                assert 0 <= v < total and v % (64 if n == 'gcount' else 256) == 0, (n, v, total)
             offs += vals
         assert len(set(offs)) == len(offs)
-        nxt = min(o for o in offs + [total] if o > lay.dslice)
-        assert lay.dslice + _abi.DF_SLICE_MAX * 8 <= nxt <= total, (lay.dslice, nxt, total)
+
+        def room(off):
+            return min(o for o in offs + [total] if o > off) - off
+        assert _abi.DF_SLICE_MAX * 8 <= room(lay.dslice), (lay.dslice, room(lay.dslice), total)
+        lc = lay.lcap
+        assert lc == lay.cap + 1 and lay.n_groups == (lc + 4095) // 4096
+        assert lc * 5 * 4 <= room(lay.pdist), (lay.pdist, room(lay.pdist))
+        for p in range(_abi.NUM_PARTS):
+            assert lc * 4 * 16 <= room(lay.feat[p]), (p, lay.feat[p], room(lay.feat[p]))
+        assert lay.counters + 16 * 4 <= lay.gcount and lay.n_groups * 5 * 4 <= room(lay.gcount), (lay.counters, lay.gcount, room(lay.gcount))
 
 
 def test_product_path_has_no_cpu_route():

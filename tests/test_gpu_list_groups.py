@@ -6,8 +6,8 @@ rank walk across tiles, the winner segments and the colour kernel's segment curs
 inside ONE group per call (asserted: the frame's 4670 rays hold 45 k survivors, up to 3497 per chunk; chunks of 1024 rays would hold
 up to 12539, three groups).  A pair's value does not depend on its position in the lists, so the two renders must agree bit for bit —
 any disagreement between the multi-group and the single-group walk shows, whether in ranks, bases, winner segments or the cursor.
-The default merge is also pinned list by list in tests/test_gpu_production_kernels.py; 'mean', 'dist' and 'mindist' are pinned
-against the oracle on a small scene only.  tests/test_hostsim_list_groups_cpu.py runs the same body through the host build."""
+The default merge is also pinned list by list in tests/test_gpu_production_kernels.py; every mode is held survivor by
+survivor to the reference's merge in tests/test_gpu_merge_modes.py. tests/test_hostsim_list_groups_cpu.py runs the same body through the host build."""
 import copy
 
 import pytest

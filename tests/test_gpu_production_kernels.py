@@ -360,6 +360,19 @@ def test_render_strict_1e4_on_well_conditioned_pixels(fr):
     assert float(err_gpu.median()) < 2e-6
 
 
+def winner_list_entries(wl_p, wcnt_p, real, g_last):
+    """The entries of one part's winner list wl_p, segment by segment: the segment of slot group g starts at the list offset of the
+    group's first pair (= the listed pairs `real`, their survivor slots ascending, of the groups before it) and holds wcnt_p[g] entries
+    (csrc/pair_lists.h).  Also tests/test_gpu_merge_modes.py."""
+    dev = wl_p.device
+    per_group = torch.bincount(real // 4096, minlength=g_last + 1)
+    off = torch.cumsum(per_group, 0) - per_group
+    gidx = torch.repeat_interleave(torch.arange(g_last + 1, device=dev), wcnt_p)
+    start = torch.cumsum(wcnt_p, 0) - wcnt_p
+    pos = off[gidx] + (torch.arange(gidx.numel(), device=dev) - start[gidx])
+    return wl_p[pos].long()
+
+
 def test_two_phase_mlp_and_winner_lists_vs_whole_field(fr):
     """The part MLPs run in two phases since round 3 (k_part_occ_all -> k_winner_lists -> k_part_rgb_all, csrc/k_mlp.hip and csrc/k_lists.hip: colour only for the pair
     that wins its survivor's max-occupancy merge).  For the WHOLE frame (2.4 M survivors, 584 slot groups: the colour kernel's
@@ -436,20 +449,13 @@ def test_two_phase_mlp_and_winner_lists_vs_whole_field(fr):
     for p in range(5):
         slots = v['l_slot'][p][:cnt[p]].long()
         real = slots[:-1]
-        # list offset of every group = pairs of the groups before it
-        per_group = torch.bincount(real // 4096, minlength=g_last + 1)
-        off = torch.cumsum(per_group, 0) - per_group
         want = (listed & (bpart == p)).nonzero(as_tuple=True)[0]             # winning survivors of part p, ascending
         want_pairs = bpair[want]
         want_per_group = torch.bincount(want // 4096, minlength=g_last + 1)
         exp_cnt = want_per_group.clone()
         exp_cnt[g_last] += 1                                                 # + the far-constant pair
         assert torch.equal(wcnt[:, p], exp_cnt), p
-        # gather the lists' entries: positions off[g] + [0, wcnt[g][p])
-        gidx = torch.repeat_interleave(torch.arange(g_last + 1, device=DEV), wcnt[:, p])
-        start = torch.cumsum(wcnt[:, p], 0) - wcnt[:, p]
-        pos = off[gidx] + (torch.arange(gidx.numel(), device=DEV) - start[gidx])
-        got = v['wl'][p][pos].long()
+        got = winner_list_entries(v['wl'][p], wcnt[:, p], real, g_last)
         assert int(got[-1]) == cnt[p] - 1                                    # the constant pair, last entry of the last segment
         assert torch.equal(got[:-1], want_pairs), p
         # colour of the winners
