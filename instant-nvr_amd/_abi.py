@@ -233,6 +233,17 @@ def _signatures_posescene():
     }
 
 
+def _signatures_surface():
+    """The same table for include/invr_surface.h (tests/test_abi_surface_cpu.py holds it against that header's text)."""
+    i32, i64, size, vp = C.c_int32, C.c_int64, C.c_size_t, C.c_void_p
+    d3, i3 = C.c_double * 3, i32 * 3                # origin / step / dims: host arrays
+    return {
+        'invr_surface_volume_workspace_bytes': (size, [i32]),
+        'invr_surface_volume': (C.c_int, [vp, i32, vp, i32, d3, d3, i3, vp, vp, vp, vp, size, vp]),
+        'invr_surface_interpolate': (C.c_int, [vp, i32, i32, vp, i32, vp, vp, i64, vp, i64, i64, vp]),
+    }
+
+
 SIGNATURES = _signatures()
 SIGNATURES_VERTEX = _signatures_vertex()
 SIGNATURES_PERCEPTUAL = _signatures_perceptual()
@@ -240,6 +251,7 @@ SIGNATURES_MESH = _signatures_mesh()
 SIGNATURES_BATCH = _signatures_batch()
 SIGNATURES_SAMPLE = _signatures_sample()
 SIGNATURES_POSESCENE = _signatures_posescene()
+SIGNATURES_SURFACE = _signatures_surface()
 EXPORTS = list(SIGNATURES)
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
 BWD_HEAD, BWD_DEFORMER, BWD_ALL = 1, 64, 127
@@ -259,7 +271,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_MESH.items())
                                           + list(SIGNATURES_BATCH.items()) + list(SIGNATURES_SAMPLE.items()) + list(SIGNATURES_VERTEX.items())
-                                          + list(SIGNATURES_POSESCENE.items())):
+                                          + list(SIGNATURES_POSESCENE.items()) + list(SIGNATURES_SURFACE.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
         if L.invr_version() != ABI_VERSION:

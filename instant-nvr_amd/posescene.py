@@ -5,7 +5,12 @@ frame, computed with psbody.mesh / CGAL) and its dataset loads them (lib/dataset
 builds them per frame from the posed vertices and the pose parameters: O(V) NumPy lines on the host, exactly the reference's, and on
 the device the LBS matrices (invr_rigid_transformation), the per-part reference sets (invr_pack_parts) and the distance volume
 (invr_distance_volume, include/invr_posescene.h).  The path reads only the last channel of `pbw` — the distance to the nearest vertex
-(inb_part_network_multiassign.py:134) — so the volume built here has that one channel."""
+(inb_part_network_multiassign.py:134) — so the volume built here has that one channel.
+
+Novel subjects: the canonical volumes of a subject (`bigpose_uv.npy`, `bigpose_bw.npy`: get_bigpose_uv / get_bigpose_blend_weights of the
+same tool, again psbody.mesh / CGAL) are built by canonical_volumes from the big-pose mesh and its per-vertex attributes through the
+closest point on the surface (invr_surface_volume / invr_surface_interpolate, include/invr_surface.h); PoseScenes.from_smpl is the
+constructor for a subject that has no precomputed volume."""
 import numpy as np
 import torch
 
@@ -24,7 +29,49 @@ class PoseFrame(dict):
     host = None
 
 
+def canonical_volumes(bigpose_vertices, faces, vertex_uv, weights=None, device='cuda', cfg=None):
+    """A subject's canonical volumes from its big-pose SMPL mesh alone — what tools/prepare_zjumocap.py computes offline with
+    psbody.mesh / CGAL: get_bigpose_uv (:177-240, `bigpose_uv.npy`) and, with `weights` (V,24), get_bigpose_blend_weights (:312-400,
+    `bigpose_bw.npy`: the interpolated skinning weights and the distance to the surface as the last channel).  bigpose_vertices (V,3),
+    faces (F,3), vertex_uv (V,2): host arrays.  The closest point of the surface for every lattice point and the interpolation are
+    include/invr_surface.h's (the contract's brute force in double; not compared with CGAL's result, which is not available here).
+    -> {'tuv' (Dx,Dy,Dz,2) float32 device tensor, 'tbounds' (2,3) float32 host array = get_bounds of the float32 vertices with
+    cfg.box_padding, 'origin', 'step' (3) float64 and 'dims' of the lattice of get_grid_points over the float64 vertices
+    [, 'tbw' (Dx,Dy,Dz,25)]}.  Asynchronous on the current stream."""
+    cfg = _config.cfg if cfg is None else cfg
+    device = torch.device(device)
+    xyz = np.asarray(bigpose_vertices)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or np.asarray(vertex_uv).shape != (xyz.shape[0], 2):
+        raise ValueError('canonical_volumes: bigpose_vertices must be (V, 3) and vertex_uv (V, 2) (got %s, %s)' % (xyz.shape, np.asarray(vertex_uv).shape))
+    if weights is not None and np.asarray(weights).shape != (xyz.shape[0], 24):
+        raise ValueError('canonical_volumes: weights must be (V, 24) (got %s)' % (np.asarray(weights).shape,))
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a), dt)).to(device)
+    origin, step, dims = PoseScenes.lattice(xyz)
+    x32 = np.ascontiguousarray(xyz, np.float32)
+    lo, hi = np.min(x32, axis=0), np.max(x32, axis=0)          # get_bounds (if_nerf_data_utils.py:689-696)
+    lo -= float(cfg.get('box_padding', 0.05))
+    hi += float(cfg.get('box_padding', 0.05))
+    d_faces = up(faces, np.int32)
+    face, bary, dist = prep.surface_volume(up(x32, np.float32), d_faces, origin, step, dims)
+    out = {'tuv': prep.surface_interpolate(up(vertex_uv, np.float32), d_faces, face, bary),
+           'tbounds': np.stack([lo, hi], axis=0).astype(np.float32), 'origin': origin, 'step': step, 'dims': list(dims)}
+    if weights is not None:
+        tbw = torch.empty(list(dims) + [25], dtype=torch.float32, device=device)
+        prep.surface_interpolate(up(weights, np.float32), d_faces, face, bary, out=tbw)
+        tbw[..., 24] = dist
+        out['tbw'] = tbw
+    return out
+
+
 class PoseScenes:
+    @classmethod
+    def from_smpl(cls, joints, parents, weights, parts, tpose, faces, vertex_uv, big_poses, cfg=None, device='cuda'):
+        """A new subject: the constructor's arguments with the SMPL faces (F,3) and per-vertex UVs (V,2) in place of the precomputed
+        canonical volume — `tuv` and `tbounds` are built by canonical_volumes from tpose (the big-pose vertices).  Once per subject: the
+        volume takes the constructor's own way in, as a host array (one read-back)."""
+        vol = canonical_volumes(tpose, faces, vertex_uv, device=device, cfg=cfg)
+        return cls(joints, parents, weights, parts, tpose, vol['tuv'].cpu().numpy(), vol['tbounds'], big_poses, cfg=cfg, device=device)
+
     def __init__(self, joints, parents, weights, parts, tpose, tuv, tbounds, big_poses, cfg=None, device='cuda'):
         """The static data of a subject as the reference's dataset holds them (tpose_dataset.py: joints.npy (24,3), parents (24),
         meta_smpl's weights (V,24) and parts (V), bigpose_vertices.npy (V,3), the canonical bigpose_uv.npy volume and its bounds
