@@ -97,6 +97,12 @@ class InvrPerceptualLayout(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ARRAYS + ('n_part1', 'n_part2', 'n_partial', 'bytes')]
 
 
+class InvrLpipsLayout(C.Structure):
+    """include/invr_lpips.h: byte offsets of every stored array of the evaluator's LPIPS in the caller's workspace."""
+    _fields_ = [('scaled', C.c_int64), ('act', C.c_int64 * 13), ('pool', C.c_int64 * 4), ('partial', C.c_int64), ('part_off', C.c_int64 * 5),
+                ('n_part', C.c_int64 * 5), ('n_partial', C.c_int64), ('bytes', C.c_int64)]
+
+
 class InvrMeshLayout(C.Structure):
     """include/invr_mesh.h: byte offsets of the per-point arrays of one surface extraction in the caller's workspace."""
     ARRAYS = ('masks', 'tcounts', 'voffsets', 'toffsets', 'counts', 'partials')
@@ -185,6 +191,18 @@ def _signatures_perceptual():
     }
 
 
+def _signatures_lpips():
+    """The same table for include/invr_lpips.h (tests/test_abi_lpips_cpu.py holds it against that header's text)."""
+    i32, i64, size, vp = C.c_int32, C.c_int64, C.c_size_t, C.c_void_p
+    return {
+        'invr_lpips_packed_floats': (i64, ()),
+        'invr_lpips_pack_weights': (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]),
+        'invr_lpips_workspace_bytes': (size, [i32, i32, i32]),
+        'invr_lpips_workspace_layout': (C.c_int, [i32, i32, i32, C.POINTER(InvrLpipsLayout)]),
+        'invr_lpips_fwd': (C.c_int, [vp, vp, vp, i32, i32, i32, vp, size, vp, vp]),
+    }
+
+
 def _signatures_mesh():
     """The same table for include/invr_mesh.h (tests/test_abi_mesh_cpu.py holds it against that header's text)."""
     i32, i64, f32, size, vp = C.c_int32, C.c_int64, C.c_float, C.c_size_t, C.c_void_p
@@ -247,6 +265,7 @@ def _signatures_surface():
 SIGNATURES = _signatures()
 SIGNATURES_VERTEX = _signatures_vertex()
 SIGNATURES_PERCEPTUAL = _signatures_perceptual()
+SIGNATURES_LPIPS = _signatures_lpips()
 SIGNATURES_MESH = _signatures_mesh()
 SIGNATURES_BATCH = _signatures_batch()
 SIGNATURES_SAMPLE = _signatures_sample()
@@ -269,7 +288,8 @@ def lib():
             raise RuntimeError('libinvr.so is not built (%s); run `python -c "import __graft_entry__ as g; g.build()"`. '
                                'There is no CPU fallback for the render path.' % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_MESH.items())
+        for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_LPIPS.items())
+                                          + list(SIGNATURES_MESH.items())
                                           + list(SIGNATURES_BATCH.items()) + list(SIGNATURES_SAMPLE.items()) + list(SIGNATURES_VERTEX.items())
                                           + list(SIGNATURES_POSESCENE.items()) + list(SIGNATURES_SURFACE.items())):
             fn = getattr(L, name)
@@ -363,6 +383,47 @@ def perceptual_views(ws, H, W):
     for k in ('g12', 'gm12', 'g11', 'gm11'):
         v[k] = view(getattr(lay, k), (64, H, W))
     return v
+
+
+LPIPS_CIN = (3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512)
+LPIPS_COUT = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
+LPIPS_BLOCK = (0, 0, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4)          # layer -> block: its map is (H >> block) x (W >> block)
+LPIPS_TAPS = (1, 3, 6, 9, 12)                                   # relu1_2, relu2_2, relu3_3, relu4_3, relu5_3
+
+
+def lpips_views(ws, H, W):
+    """Zero-copy tensor views of every array invr_lpips_fwd(keep = 1) leaves in the workspace `ws` (uint8 tensor): the scaled planar
+    input, the 13 activations, the 4 pooled maps and the partial sums (16 pixels each) of each tap."""
+    lay = InvrLpipsLayout()
+    check(lib().invr_lpips_workspace_layout(H, W, 1, C.byref(lay)))
+
+    def view(off, shape, dtype=torch.float32):
+        count = 1
+        for d in shape:
+            count *= d
+        return ws[off:off + count * torch.empty((), dtype=dtype).element_size()].view(dtype).view(*shape)
+    v = {'layout': lay, 'scaled': view(lay.scaled, (2, 3, H, W)),
+         'act': [view(lay.act[l], (2, LPIPS_COUT[l], H >> LPIPS_BLOCK[l], W >> LPIPS_BLOCK[l])) for l in range(13)],
+         'pool': [view(lay.pool[b], (2, LPIPS_CIN[LPIPS_TAPS[b] + 1], H >> (b + 1), W >> (b + 1))) for b in range(4)],
+         'partial': [view(lay.partial + 8 * lay.part_off[t], (lay.n_part[t],), torch.float64) for t in range(5)]}
+    return v
+
+
+def lpips_pack(conv_w, conv_b, lin_w, shift, scale, packed=None):
+    """The packed weight image of invr_lpips_pack_weights from the 13 (out, in, 3, 3) weights, (out) biases, the five lin vectors (C)
+    and the scaling layer's shift / scale (3) — device tensors."""
+    L = lib()
+    ws, bs, ls = [f32c(t) for t in conv_w], [f32c(t) for t in conv_b], [f32c(t).reshape(-1) for t in lin_w]
+    assert [tuple(t.shape) for t in ws] == [(o, i, 3, 3) for i, o in zip(LPIPS_CIN, LPIPS_COUT)], [tuple(t.shape) for t in ws]
+    assert [tuple(t.shape) for t in bs] == [(o,) for o in LPIPS_COUT], [tuple(t.shape) for t in bs]
+    assert [tuple(t.shape) for t in ls] == [(LPIPS_COUT[l],) for l in LPIPS_TAPS], [tuple(t.shape) for t in ls]
+    sh, sc = f32c(shift).reshape(-1), f32c(scale).reshape(-1)
+    assert sh.numel() == 3 and sc.numel() == 3
+    if packed is None:
+        packed = torch.empty(L.invr_lpips_packed_floats(), device=ws[0].device)
+    arr = lambda ts: (C.c_void_p * len(ts))(*[ptr(t).value for t in ts])
+    check(L.invr_lpips_pack_weights(arr(ws), arr(bs), arr(ls), ptr(sh), ptr(sc), ptr(packed), stream_ptr()))
+    return packed
 
 
 def mesh_views(ws, dims):

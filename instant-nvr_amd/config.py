@@ -90,6 +90,10 @@ DEFAULTS = {
     # image loss: configs/inb/inb_377.yaml sets use_lpips True (VGG19 from torchvision, absent on this image).  The stand-alone
     # default is the plain MSE; adopt() takes the host's value and NetworkWrapper raises if no perceptual loss can be had.
     'use_lpips': False, 'use_ssim': False, 'use_fourier': False, 'use_tv_image': False, 'vgg19_weights': None,
+    # evaluation (invr.evaluator): LPIPS v0.1 net='vgg' on the HIP kernels (invr.lpips_eval over csrc/k_lpips.hip).  The weights come
+    # from Evaluator's lpips= argument, else from these two files (a torchvision VGG16 state dict and the lpips package's vgg.pth), else
+    # from the `lpips` package of the host process; eval_fused_lpips False keeps a recognised module on its own torch call.
+    'eval_fused_lpips': True, 'lpips_vgg16_weights': None, 'lpips_lin_weights': None,
     # training patches (invr.trainset): the window side of random_crop_image (lib/config/config.py:252) and the semantic mask the crop
     # rectangle is taken from ('' = the body mask; the training_stages of the INB yamls switch it to 'head' between epochs)
     'patch_size': 64, 'sample_focus': '',

@@ -13,8 +13,18 @@ reference's per-frame rules are applied:
                                  uint8 device image — a device-to-host copy per frame, the one place a frame waits for the device.  (The
                                  reference's test_full False branch writes them whatever fast_eval says; here fast_eval decides in both.)
   cfg.eval_part                  not built: raises at construction
-LPIPS (:118-122) needs the `lpips` package and its VGG weights in the host process; where it cannot be imported the list stays empty,
-the printed summary omits it and a warning is issued once — no value is ever made up.
+LPIPS (:118-122, lp.LPIPS(net='vgg') on the two whole frames, cfg.test_full only) runs on the device too (invr.lpips_eval over
+csrc/k_lpips.hip: a VGG16 forward of exact-fp32 matrix products, the distance in float64, bit-reproducible, no host round trip): its
+device scalar joins the frame's pending results and is read back with them.  No weights ship here; at the first test_full frame they
+are resolved from, in this order,
+  1. Evaluator's lpips= argument: an invr.lpips_eval.LpipsVgg, or a module that is recognisably lpips.LPIPS(net='vgg')
+  2. cfg.lpips_vgg16_weights + cfg.lpips_lin_weights: a torchvision VGG16 state dict and the lpips package's vgg.pth
+  3. `import lpips` in the host process
+A recognised module takes the device path unless cfg.eval_fused_lpips is False (then its own torch call runs, as does any module that
+is not recognised).  The device path copies a module's weights and leaves the module alone; the torch call moves it to the frames'
+device, puts it in eval mode and switches its gradients off, a module handed in as lpips= included.  The flag has no effect on an
+LpipsVgg or on the two files: they have no torch call.  An argument or files that cannot be used raise.  With nothing available the list stays empty, the printed
+summary omits it and a warning is issued once — no value is ever made up.
 """
 import os
 import sys
@@ -87,8 +97,9 @@ def fill_image(img, batch):
 
 
 class Evaluator:
-    def __init__(self, cfg=None):
+    def __init__(self, cfg=None, lpips=None):
         self.cfg = default_cfg() if cfg is None else cfg
+        self._lpips_arg = lpips          # an LpipsVgg, a torch module, or None
         if _cfg_get(self.cfg, 'eval_part', '') != '':
             raise ValueError('invr: unsupported configuration eval_part = %r — the per-part evaluation mask (if_nerf.py:91-94) is not built'
                              % (_cfg_get(self.cfg, 'eval_part', ''),))
@@ -96,10 +107,11 @@ class Evaluator:
         self.last_blocks = None          # host copy of the result blocks of the last read-back, (frames, 64) uint8
         self._ring = []                  # device tensors (RING_CHUNK, 64) uint8
         self._frames = []                # (H, W, test_full) per pending frame, in ring order
-        self._lpips_dev = []             # device scalars of the pending frames (when lpips is importable)
+        self._lpips_dev = []             # device scalars of the pending test_full frames: float64 of the device path, float32 of the torch call
         self._read = None                # decoded blocks of the pending frames once read back
         self._ws = {}                    # (device, stream) -> (H, W, workspace)
-        self._loss_fn = None
+        self._loss_fn = None             # the torch module of the torch path
+        self._lpips_fused = None         # the LpipsVgg of the device path
         self._lpips_state = None         # None = not tried, True / False
 
     # ---- switches (read at every call: the reference reads the global cfg) ----
@@ -126,20 +138,43 @@ class Evaluator:
             self._ring.append(M.new_results(RING_CHUNK, device))
         return self._ring[k // RING_CHUNK][k % RING_CHUNK]
 
-    def _lpips(self, img_pred, img_gt):
-        if self._lpips_state is None:
+    def _lpips_resolve(self, device):
+        """-> (LpipsVgg or None, torch module or None) by the order of the module docstring; (None, None) after the one warning when
+        nothing is available.  What the caller NAMED — the argument, the two files — raises if it cannot be used."""
+        from . import lpips_eval
+        fused = bool(_cfg_get(self.cfg, 'eval_fused_lpips', True))
+        arg = self._lpips_arg
+        if isinstance(arg, lpips_eval.LpipsVgg):
+            return arg, None
+        module = arg
+        if module is None:
+            vgg, lin = _cfg_get(self.cfg, 'lpips_vgg16_weights', None), _cfg_get(self.cfg, 'lpips_lin_weights', None)
+            if vgg and lin:
+                return lpips_eval.LpipsVgg.from_files(vgg, lin, device=device), None
             try:
                 import lpips as lp
-                self._loss_fn = lp.LPIPS(net='vgg', verbose=False).to(img_pred.device).eval()
-                for p in self._loss_fn.parameters():
-                    p.requires_grad_(False)
-                self._lpips_state = True
+                module = lp.LPIPS(net='vgg', verbose=False)
             except Exception as e:          # the package, or its weights, are not there
-                self._lpips_state = False
                 warnings.warn('invr Evaluator: LPIPS is not computed (%s: %s); the lpips list stays empty' % (type(e).__name__, e))
+                return None, None
+        net = lpips_eval.LpipsVgg.from_module(module, device=device) if fused else None      # (copies the weights: the module stays as it is)
+        if net is not None:
+            return net, None
+        module = module.to(device).eval()          # the torch path calls the module itself: moved, eval mode, no gradients — the caller's too
+        for p in module.parameters():
+            p.requires_grad_(False)
+        return None, module
+
+    def _lpips(self, img_pred, img_gt):
+        if self._lpips_state is None:
+            self._lpips_fused, self._loss_fn = self._lpips_resolve(img_pred.device)
+            self._lpips_state = self._lpips_fused is not None or self._loss_fn is not None
         if self._lpips_state:
-            with torch.no_grad():
-                self._lpips_dev.append(self._loss_fn(img_pred.permute(2, 0, 1)[None], img_gt.permute(2, 0, 1)[None])[0].detach())
+            if self._lpips_fused is not None:
+                self._lpips_dev.append(self._lpips_fused(img_pred, img_gt))
+            else:
+                with torch.no_grad():
+                    self._lpips_dev.append(self._loss_fn(img_pred.permute(2, 0, 1)[None], img_gt.permute(2, 0, 1)[None])[0].detach())
 
     def _write_images(self, u8_pred, u8_gt, batch, epoch):
         result_dir = os.path.join(self.result_dir, 'comparison_epoch%d' % epoch if epoch != -1 else 'comparison')
