@@ -109,6 +109,11 @@ class InvrMeshLayout(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ARRAYS + ('n_points', 'n_blocks', 'bytes')]
 
 
+class InvrGeoOut(C.Structure):
+    """include/invr_geomaps.h: the geometry outputs of invr_render_fwd_geo (NULL = not formed)."""
+    _fields_ = [('level', C.c_float), ('depth_map', C.c_void_p), ('surf_index', C.c_void_p), ('surf_depth', C.c_void_p)]
+
+
 def _signatures():
     """name -> (restype, argtypes) of every prototype of include/invr.h, in the header's order (tests/test_abi_symbols.py holds each
     entry against the header's text).  vp = any data pointer: device tensors, host arrays and the stream go through as addresses."""
@@ -262,6 +267,17 @@ def _signatures_surface():
     }
 
 
+def _signatures_geomaps():
+    """The same table for include/invr_geomaps.h (tests/test_geomaps_abi_cpu.py holds it against that header's text)."""
+    i32, i64, f32, vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
+    return {
+        'invr_depth_fwd': (C.c_int, [vp, vp, vp, vp, i64, i32, f32, f32, vp, vp, vp, vp]),
+        'invr_render_fwd_geo': (C.c_int, SIGNATURES['invr_render_fwd_tracked'][1] + [C.POINTER(InvrGeoOut)]),
+        'invr_surface_stencil': (C.c_int, [vp, vp, vp, vp, i64, f32, vp, vp, vp]),
+        'invr_stencil_normals': (C.c_int, [vp, vp, i64, vp, vp, vp]),
+    }
+
+
 SIGNATURES = _signatures()
 SIGNATURES_VERTEX = _signatures_vertex()
 SIGNATURES_PERCEPTUAL = _signatures_perceptual()
@@ -271,6 +287,8 @@ SIGNATURES_BATCH = _signatures_batch()
 SIGNATURES_SAMPLE = _signatures_sample()
 SIGNATURES_POSESCENE = _signatures_posescene()
 SIGNATURES_SURFACE = _signatures_surface()
+SIGNATURES_GEOMAPS = _signatures_geomaps()
+SIZEOF_GEO_OUT = 10      # include/invr_geomaps.h INVR_SIZEOF_GEO_OUT
 EXPORTS = list(SIGNATURES)
 ABI_VERSION = 2          # include/invr.h INVR_ABI_VERSION
 BWD_HEAD, BWD_DEFORMER, BWD_ALL = 1, 64, 127
@@ -291,14 +309,15 @@ def lib():
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_LPIPS.items())
                                           + list(SIGNATURES_MESH.items())
                                           + list(SIGNATURES_BATCH.items()) + list(SIGNATURES_SAMPLE.items()) + list(SIGNATURES_VERTEX.items())
-                                          + list(SIGNATURES_POSESCENE.items()) + list(SIGNATURES_SURFACE.items())):
+                                          + list(SIGNATURES_POSESCENE.items()) + list(SIGNATURES_SURFACE.items())
+                                          + list(SIGNATURES_GEOMAPS.items())):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, list(argtypes)
         if L.invr_version() != ABI_VERSION:
             raise RuntimeError('libinvr.so speaks ABI version %d, this binding %d (include/invr.h INVR_ABI_VERSION): rebuild the library '
                                '(python -m invr.build)' % (L.invr_version(), ABI_VERSION))
         for i, t in enumerate((InvrGrid, InvrMlp, InvrPart, InvrModel, InvrScene, InvrWsLayout, InvrMlpBwdOut, InvrAdamTensor, InvrTrainGrads,
-                               InvrDeformBwdOut)):
+                               InvrDeformBwdOut, InvrGeoOut)):
             if L.invr_sizeof(i) != C.sizeof(t):
                 raise RuntimeError('libinvr ABI mismatch: struct %s is %d bytes in the library, %d in the binding'
                                    % (t.__name__, L.invr_sizeof(i), C.sizeof(t)))

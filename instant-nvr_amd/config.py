@@ -87,6 +87,9 @@ DEFAULTS = {
     # 2^24 had the lowest frame time of 2^20 / 2^22 / 2^24 on the bench frame, for 453 MB of derived tables; 2^22 keeps three quarters
     # of the gain in 71 MB (profiles/vertex_tables.md)
     'eval_vertex_rows': 1 << 24,
+    # eval frames also carry depth_map and surf_depth (invr.geomaps, include/invr_geomaps.h): the depth pass behind the compositing;
+    # surface_level = the occupancy the first crossing is taken at (the reference treats |tocc - 0.5| < 0.02 as the surface, inb_renderer.py:81)
+    'render_depth': False, 'surface_level': 0.5,
     # image loss: configs/inb/inb_377.yaml sets use_lpips True (VGG19 from torchvision, absent on this image).  The stand-alone
     # default is the plain MSE; adopt() takes the host's value and NetworkWrapper raises if no perceptual loss can be had.
     'use_lpips': False, 'use_ssim': False, 'use_fourier': False, 'use_tv_image': False, 'vgg19_weights': None,

@@ -12,6 +12,7 @@
 #include "grid_level.h"
 #include "train.h"
 #include "../../include/invr_vertex.h"
+#include "../../include/invr_geomaps.h"
 static_assert(GRID_VERTEX_MAX_ROWS == INVR_VERTEX_MAX_ROWS, "one limit");
 
 static thread_local char g_err[512] = "";
@@ -37,6 +38,7 @@ extern "C" size_t invr_sizeof(int32_t which) {
         case 7: return sizeof(InvrAdamTensor);
         case 8: return sizeof(InvrTrainGrads);
         case 9: return sizeof(InvrDeformBwdOut);
+        case INVR_SIZEOF_GEO_OUT: return sizeof(InvrGeoOut);
         default: return 0;
     }
 }
@@ -381,6 +383,11 @@ struct FrameCall {
     bool geometry_only;      // stop behind the warp: pair lists, flags, counters and z_vals only
     bool may_reorder;        // an eval call: the depth-windowed survivor order is allowed (the training calls keep ray-major)
     uint64_t* raw_dirty;     // invr_render_fwd_tracked: raw's zero rows are tracked, not rewritten
+    // invr_render_fwd_geo (include/invr_geomaps.h): the depth pass behind the compositing; all NULL = no such launch
+    float geo_level;
+    float* depth_map;
+    int32_t* surf_index;
+    float* surf_depth;
 };
 
 static int render_impl(const FrameCall& c) {
@@ -481,6 +488,8 @@ static int render_impl(const FrameCall& c) {
     if (!c.geometry_only) {
         ProfStage ps(INVR_STAGE_COMPOSITE, st);
         if (launch_merge_composite(a, w, c.rgb_map, c.acc_map, c.raw, c.occ, c.weights, st, reinterpret_cast<unsigned long long*>(c.raw_dirty))) return 1;
+        // the same Workspace object: the survivor order of this frame (w.ord_rows) is the one the compositing just read
+        if ((c.depth_map || c.surf_index || c.surf_depth) && launch_geo_depth_merged(a, w, c.jitter ? c.z_vals : nullptr, c.geo_level, c.depth_map, c.surf_index, c.surf_depth, st)) return 1;
     }
     if (g_prof_on) ++g_prof_renders;
     return 0;                   // (stats were exported by the KNN stage: the counters are final once the pair lists are)
@@ -504,6 +513,17 @@ extern "C" int invr_render_fwd(const InvrScene* scene, const InvrModel* model,
 
 extern "C" size_t invr_raw_dirty_bytes(int64_t rows) { return rows > 0 ? (size_t)cdiv(rows, 64) * sizeof(uint64_t) : 0; }
 
+// the argument rules of a tracked raw buffer (invr_render_fwd_tracked, invr_render_fwd_geo with raw_dirty)
+static int check_tracked(const char* who, const float* raw, const float* occ, const float* weights, int64_t n_rays, int32_t n_samples,
+                         const uint64_t* raw_dirty, int64_t raw_rows) {
+    INVR_CHECK(raw && raw_dirty, "%s: null raw / raw_dirty", who);
+    INVR_CHECK(!occ && !weights, "%s: occ and weights must be NULL (occ is raw's fourth channel; the weights belong to the training calls)", who);
+    INVR_CHECK(n_rays >= 0 && n_samples >= 1 && raw_rows >= n_rays * (int64_t)n_samples, "%s: raw_rows %lld < n_rays * n_samples", who,
+               (long long)raw_rows);
+    INVR_CHECK(((uintptr_t)raw & 15) == 0 && ((uintptr_t)raw_dirty & 7) == 0, "%s: raw must be 16-byte, raw_dirty 8-byte aligned", who);
+    return 0;
+}
+
 extern "C" int invr_render_fwd_tracked(const InvrScene* scene, const InvrModel* model,
                                        const float* ray_o, const float* ray_d, const float* near, const float* far,
                                        const float* jitter, int64_t n_rays, int32_t n_samples,
@@ -511,11 +531,7 @@ extern "C" int invr_render_fwd_tracked(const InvrScene* scene, const InvrModel* 
                                        float* z_vals, int32_t* stats,
                                        void* workspace, size_t workspace_bytes, int64_t max_active, void* stream,
                                        uint64_t* raw_dirty, int64_t raw_rows) {
-    INVR_CHECK(raw && raw_dirty, "invr_render_fwd_tracked: null raw / raw_dirty");
-    INVR_CHECK(!occ && !weights, "invr_render_fwd_tracked: occ and weights must be NULL (occ is raw's fourth channel; the weights belong to the training calls)");
-    INVR_CHECK(n_rays >= 0 && n_samples >= 1 && raw_rows >= n_rays * (int64_t)n_samples, "invr_render_fwd_tracked: raw_rows %lld < n_rays * n_samples",
-               (long long)raw_rows);
-    INVR_CHECK(((uintptr_t)raw & 15) == 0 && ((uintptr_t)raw_dirty & 7) == 0, "invr_render_fwd_tracked: raw must be 16-byte, raw_dirty 8-byte aligned");
+    if (check_tracked("invr_render_fwd_tracked", raw, occ, weights, n_rays, n_samples, raw_dirty, raw_rows)) return 1;
     FrameCall c = {};
     c.scene = scene; c.model = model;
     c.ray_o = ray_o; c.ray_d = ray_d; c.near = near; c.far = far; c.jitter = jitter;
@@ -524,6 +540,28 @@ extern "C" int invr_render_fwd_tracked(const InvrScene* scene, const InvrModel* 
     c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.max_active = max_active; c.stream = stream;
     c.may_reorder = true;
     c.raw_dirty = raw_dirty;
+    return render_impl(c);
+}
+
+extern "C" int invr_render_fwd_geo(const InvrScene* scene, const InvrModel* model,
+                                   const float* ray_o, const float* ray_d, const float* near, const float* far,
+                                   const float* jitter, int64_t n_rays, int32_t n_samples,
+                                   float* rgb_map, float* acc_map, float* raw, float* occ, float* weights,
+                                   float* z_vals, int32_t* stats,
+                                   void* workspace, size_t workspace_bytes, int64_t max_active, void* stream,
+                                   uint64_t* raw_dirty, int64_t raw_rows, const InvrGeoOut* geo) {
+    if (raw_dirty && check_tracked("invr_render_fwd_geo", raw, occ, weights, n_rays, n_samples, raw_dirty, raw_rows)) return 1;
+    INVR_CHECK(!geo || isfinite(geo->level), "invr_render_fwd_geo: level must be finite");
+    INVR_CHECK(!geo || !jitter || z_vals, "invr_render_fwd_geo: a call with jitter needs z_vals (the depths the maps are formed with)");
+    FrameCall c = {};
+    c.scene = scene; c.model = model;
+    c.ray_o = ray_o; c.ray_d = ray_d; c.near = near; c.far = far; c.jitter = jitter;
+    c.n_rays = n_rays; c.n_samples = n_samples;
+    c.rgb_map = rgb_map; c.acc_map = acc_map; c.raw = raw; c.occ = occ; c.weights = weights; c.z_vals = z_vals; c.stats = stats;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.max_active = max_active; c.stream = stream;
+    c.may_reorder = true;
+    c.raw_dirty = raw_dirty;
+    if (geo) { c.geo_level = geo->level; c.depth_map = geo->depth_map; c.surf_index = geo->surf_index; c.surf_depth = geo->surf_depth; }
     return render_impl(c);
 }
 

@@ -215,3 +215,6 @@ struct MlpAllArgs {               // k_part_mlp_all
 int launch_part_mlp_all(const MlpAllArgs& a, const Workspace& w, hipStream_t st);
 int launch_merge_composite(const RenderArgs& a, const Workspace& w, float* rgb_map, float* acc_map, float* raw,
                            float* occ, float* weights, hipStream_t st, unsigned long long* raw_dirty = nullptr);     // raw_dirty: invr_render_fwd_tracked
+// k_geomaps.hip (include/invr_geomaps.h): depth / first crossing per ray from the merged results a render left in `w`; z_vals or null
+int launch_geo_depth_merged(const RenderArgs& a, const Workspace& w, const float* z_vals, float level, float* depth_map,
+                            int32_t* surf_index, float* surf_depth, hipStream_t st);

@@ -7,6 +7,7 @@ they run where the reference is absent (the GPU box):
                   the whole HxW image with zeros outside mask_at_box
   run_mesh      : one surface mesh (.ply) per frame: what the reference's tmesh hooks and visualizer (lib/visualizers/if_nerf.py:133-160)
                   are for, as the posed mesh (invr.mesh)
+  run_geometry  : depth, first-crossing and surface-normal maps per frame (invr.geomaps): the keys lib/visualizers/if_nerf.py:63-121 reads
   save_model / load_network : the reference's .pth layout {net, optim, scheduler, recorder, epoch}
                   (lib/utils/net_utils.py:461-528) so checkpoints interchange in both directions
 """
@@ -173,6 +174,22 @@ def run_mesh(net, batches, out_dir, level=0.1, voxel_size=None, view_from=None, 
         out['vertices'].append(int(m['vertices'].shape[0]))
         out['triangles'].append(int(m['triangles'].shape[0]))
     return out
+
+
+def run_geometry(net, batches, on_frame=None, level=None, h=0.005, normals=True, device='cuda'):
+    """The geometry maps of a sequence (invr.geomaps.geometry_maps: depth_map, surf_depth, surf_mask, surf_normal, acc_map, rgb_map per
+    ray of mask_at_box, device tensors; geomaps.image_of scatters one to the image).  on_frame(i, maps) receives every frame's dict;
+    without a callback -> the list of dicts."""
+    from . import geomaps
+    out = []
+    for i, batch in enumerate(batches):
+        batch = {k: (v.to(device) if torch.is_tensor(v) and not (k in HOST_KEYS and not v.is_cuda) else v) for k, v in batch.items()}
+        maps = geomaps.geometry_maps(net, batch, level=level, h=h, normals=normals)
+        if on_frame is not None:
+            on_frame(i, maps)
+        else:
+            out.append(maps)
+    return None if on_frame is not None else out
 
 
 def run_poses(net, scenes, frames, camera, in_flight=None, on_frame=None, renderer=None):

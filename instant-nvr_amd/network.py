@@ -355,7 +355,7 @@ class Network(nn.Module):
         return out
 
     def render_rays(self, batch, ray_o, ray_d, near, far, n_samples, jitter=None, want_raw=True,
-                    want_weights=False, max_active=0, stream=None, raw_out=None, raw_dirty=None):
+                    want_weights=False, max_active=0, stream=None, raw_out=None, raw_dirty=None, want_depth=False, level=0.5):
         """One invr_render_fwd call over a ray list (n,3)/(n,).  `batch` is the collated batch dict
         or a RenderContext from prepare().  Returns a dict of device tensors.
         stream: launch on THAT torch stream instead of the current one while every tensor (outputs, workspace) still comes from the
@@ -365,7 +365,9 @@ class Network(nn.Module):
         raw_dirty: with raw_out, the buffer's dirty words (int64, one bit per 16-byte row of ALL of raw_out, at least
         ceil(rows / 64) of them): the call goes through invr_render_fwd_tracked, which stores only the rows that are non-zero now or
         were on entry and keeps the words current (include/invr.h: a clear bit = the row holds zeros, on entry and on exit).  A new
-        pair starts zeroed, or with raw uninitialised and every word -1.  Not with want_weights."""
+        pair starts zeroed, or with raw uninitialised and every word -1.  Not with want_weights.
+        want_depth: the call goes through invr_render_fwd_geo (include/invr_geomaps.h) and the result gains depth_map (n,), surf_index
+        (n,) int32 — the first sample whose occupancy reaches `level`, -1 if none — and surf_depth (n,), the depth of that crossing."""
         L = _abi.lib()
         dev = ray_o.device
         ctx = batch if isinstance(batch, RenderContext) else self.prepare(batch)
@@ -382,6 +384,12 @@ class Network(nn.Module):
         if want_weights:
             out['weights'] = torch.empty(n, S, device=dev)
             out['z_vals'] = torch.empty(n, S, device=dev)
+        if want_depth:
+            out['depth_map'] = torch.empty(n, device=dev)
+            out['surf_index'] = torch.empty(n, dtype=torch.int32, device=dev)
+            out['surf_depth'] = torch.empty(n, device=dev)
+            if jitter is not None and 'z_vals' not in out:
+                out['z_vals'] = torch.empty(n, S, device=dev)          # (the jittered depths the maps are formed with)
         if jitter is not None:
             jitter = f(jitter)
         nbytes = L.invr_workspace_bytes(n, S, max_active)
@@ -392,9 +400,14 @@ class Network(nn.Module):
                 _abi.ptr(out.get('z_vals')), _abi.ptr(out['stats'], torch.int32),
                 C.c_void_p(ws.data_ptr()), nbytes, max_active, _abi.stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream))
         tracked = want_raw and raw_out is not None and raw_dirty is not None
+        rows = 0
         if tracked:
             rows = raw_out.numel() // 4
             assert raw_out.dtype == torch.float32 and raw_out.is_contiguous() and raw_dirty.numel() * 64 >= rows, 'raw_dirty: one bit per row of raw_out'
+        if want_depth:
+            geo = _abi.InvrGeoOut(float(level), out['depth_map'].data_ptr(), out['surf_index'].data_ptr(), out['surf_depth'].data_ptr())
+            _abi.check(L.invr_render_fwd_geo(*args, _abi.ptr(raw_dirty if tracked else None, torch.int64), rows, C.byref(geo)))
+        elif tracked:
             _abi.check(L.invr_render_fwd_tracked(*args, _abi.ptr(raw_dirty, torch.int64), rows))
         else:
             _abi.check(L.invr_render_fwd(*args))

@@ -315,6 +315,8 @@ class _PendingFrame:
         out = self.out
         cur = torch.cuda.current_stream(out['rgb_map'].device)
         dev = {'rgb_map': out['rgb_map'][None], 'acc_map': out['acc_map'][None]}
+        for k in r._geo_keys():
+            dev[k] = out[k][None]
         if r.want_raw:
             dev['raw'] = out['raw'][None]
             dev['occ'] = out['occ'][None, :, None]
@@ -357,6 +359,17 @@ class Renderer:
         self.lazy_device_budget = int(self.cfg.get('lazy_device_budget', 8 << 30)) if hasattr(self.cfg, 'get') else 8 << 30
         self._lazy_live = []
         self._cap_hint = None
+        # eval frames with geometry maps (cfg.render_depth; training-mode renders ignore it): depth_map and surf_depth travel with the image maps
+        self.render_depth = bool(self.cfg.get('render_depth', False)) if hasattr(self.cfg, 'get') else False
+        self.surface_level = float(self.cfg.get('surface_level', 0.5)) if hasattr(self.cfg, 'get') else 0.5
+
+    GEO_KEYS = ('depth_map', 'surf_depth')
+
+    def _geo_keys(self):
+        return self.GEO_KEYS if self.render_depth else ()
+
+    def _geo_kw(self):
+        return {'want_depth': True, 'level': self.surface_level} if self.render_depth else {}
 
     def render(self, batch, test=False, epoch=-1):
         cfg = self.cfg
@@ -384,7 +397,8 @@ class Renderer:
             # statistics block synchronises.  eval_to_cpu = False: full capacity, and the asynchronous caller checks last_stats[6] itself
             cap = cap_bound(n_samp, self._cap_hint) if self.adaptive_cap and self.eval_to_cpu else 0
             call = lambda c: self.net.render_rays(batch, ray_o[0, sl], ray_d[0, sl], near[0, sl], far[0, sl], S,
-                                                  jitter=None if jitter is None else jitter[sl], want_raw=self.want_raw, max_active=c)
+                                                  jitter=None if jitter is None else jitter[sl], want_raw=self.want_raw, max_active=c,
+                                                  **self._geo_kw())
             out = call(cap)
             if self.eval_to_cpu:
                 st = out['stats'].cpu()
@@ -397,6 +411,8 @@ class Renderer:
             outs.append(out)
         cat = (lambda k: outs[0][k]) if len(outs) == 1 else (lambda k: torch.cat([o[k] for o in outs], 0))
         ret = {'rgb_map': cat('rgb_map')[None], 'acc_map': cat('acc_map')[None]}
+        for k in self._geo_keys():
+            ret[k] = cat(k)[None]
         if self.want_raw:
             ret['raw'] = cat('raw')[None]
             ret['occ'] = cat('occ')[None, :, None]
@@ -438,7 +454,7 @@ class Renderer:
         self._raw_numel = max(getattr(self, '_raw_numel', 0), n_samp * 4)          # grow-only, renderer-wide: every lane's raw buffer fits the largest frame seen
         ctx = self.net.prepare(batch)          # on the caller's stream: a stale row-sum table is rebuilt in front of every lane
         call = lambda c, st, raw_kw: self.net.render_rays(ctx, ray_o, ray_d, near, far, S, jitter=jitter, want_raw=self.want_raw, max_active=c,
-                                                          stream=st, **raw_kw)
+                                                          stream=st, **raw_kw, **self._geo_kw())
         pend = _PendingFrame(self, lane, call, cap, (batch, ctx, ray_o, ray_d, near, far, jitter))
         pend.launch()
         lane.pending = pend
@@ -449,7 +465,7 @@ class Renderer:
             if cap > 2 * self._cap_hint:
                 lane.ws = None
             self._cap_hint = int(CAP_HEADROOM_FIRST * self._cap_hint)           # later frames of a sequence rarely force a regrowth
-        keys = ('rgb_map', 'acc_map') + (('raw', 'occ') if self.want_raw else ())
+        keys = ('rgb_map', 'acc_map') + self._geo_keys() + (('raw', 'occ') if self.want_raw else ())
         if self.eval_to_cpu:
             return self._track_lazy(LazyHostRet({}, {}, self.pin_host, pending=pend, keys=keys))
         return LazyDevRet(pend, keys)
