@@ -97,6 +97,12 @@ class InvrPerceptualLayout(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ARRAYS + ('n_part1', 'n_part2', 'n_partial', 'bytes')]
 
 
+class InvrImglossLayout(C.Structure):
+    """include/invr_imgloss.h: byte offsets of every array of the SSIM / TV image terms in the caller's workspace."""
+    ARRAYS = ('rank', 'img', 'mom', 'smap', 'pqr', 'occ', 'tvmax', 'partial', 'out8', 'gimg')
+    _fields_ = [(k, C.c_int64) for k in ARRAYS + ('n_ssim', 'n_tv', 'n_partial', 'bytes')]
+
+
 class InvrLpipsLayout(C.Structure):
     """include/invr_lpips.h: byte offsets of every stored array of the evaluator's LPIPS in the caller's workspace."""
     _fields_ = [('scaled', C.c_int64), ('act', C.c_int64 * 13), ('pool', C.c_int64 * 4), ('partial', C.c_int64), ('part_off', C.c_int64 * 5),
@@ -196,6 +202,25 @@ def _signatures_perceptual():
     }
 
 
+def _signatures_imgloss():
+    """The same table for include/invr_imgloss.h (tests/test_abi_imgloss_cpu.py holds it against that header's text)."""
+    i32, i64, f32, size, vp = C.c_int32, C.c_int64, C.c_float, C.c_size_t, C.c_void_p
+    ws = [vp, size]                                # workspace, workspace_bytes
+    obj = [f32, f32, f32, i32]                     # w_pair, w_dist, w_off, use_pair
+    return {
+        'invr_imgloss_workspace_bytes': (size, [i32, i32, i32]),
+        'invr_imgloss_workspace_layout': (C.c_int, [i32, i32, i32, C.POINTER(InvrImglossLayout)]),
+        'invr_ssim_fwd': (C.c_int, [vp, vp, vp, vp, i32, i64, i32, i32] + ws + [vp, vp]),
+        'invr_ssim_bwd': (C.c_int, [vp, vp, i32, i64, i32, i32] + ws + [vp, vp, vp]),
+        'invr_tv_fwd': (C.c_int, [vp, vp, vp, vp, i64, i32, i32] + ws + [vp, vp]),
+        'invr_tv_bwd': (C.c_int, [vp, i64, i32, i32] + ws + [vp, vp, vp]),
+        'invr_train_loss_ssim_fwd': (C.c_int, [vp, vp, vp, vp, i32, vp, vp, i64, i32, i32] + obj + ws + [vp, vp, vp]),
+        'invr_train_loss_ssim_bwd': (C.c_int, [vp, vp, i32, vp, i64, i32, i32] + obj + ws + [vp, vp, vp, vp, vp]),
+        'invr_train_loss_tv_fwd': (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i32, i32] + obj + ws + [vp, vp, vp]),
+        'invr_train_loss_tv_bwd': (C.c_int, [vp, vp, i64, i32, i32] + obj + ws + [vp, vp, vp, vp, vp]),
+    }
+
+
 def _signatures_lpips():
     """The same table for include/invr_lpips.h (tests/test_abi_lpips_cpu.py holds it against that header's text)."""
     i32, i64, size, vp = C.c_int32, C.c_int64, C.c_size_t, C.c_void_p
@@ -281,6 +306,7 @@ def _signatures_geomaps():
 SIGNATURES = _signatures()
 SIGNATURES_VERTEX = _signatures_vertex()
 SIGNATURES_PERCEPTUAL = _signatures_perceptual()
+SIGNATURES_IMGLOSS = _signatures_imgloss()
 SIGNATURES_LPIPS = _signatures_lpips()
 SIGNATURES_MESH = _signatures_mesh()
 SIGNATURES_BATCH = _signatures_batch()
@@ -306,7 +332,8 @@ def lib():
             raise RuntimeError('libinvr.so is not built (%s); run `python -c "import __graft_entry__ as g; g.build()"`. '
                                'There is no CPU fallback for the render path.' % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_LPIPS.items())
+        for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(SIGNATURES_PERCEPTUAL.items()) + list(SIGNATURES_IMGLOSS.items())
+                                          + list(SIGNATURES_LPIPS.items())
                                           + list(SIGNATURES_MESH.items())
                                           + list(SIGNATURES_BATCH.items()) + list(SIGNATURES_SAMPLE.items()) + list(SIGNATURES_VERTEX.items())
                                           + list(SIGNATURES_POSESCENE.items()) + list(SIGNATURES_SURFACE.items())
@@ -402,6 +429,23 @@ def perceptual_views(ws, H, W):
     for k in ('g12', 'gm12', 'g11', 'gm11'):
         v[k] = view(getattr(lay, k), (64, H, W))
     return v
+
+
+def imgloss_views(ws, H, W, window=11):
+    """Zero-copy tensor views of every array the SSIM / TV image terms keep in the workspace `ws` (uint8 tensor): the assembled images,
+    the five filtered maps, S, p / q / r, mask_gt, the partial sums and the gradient of the assembled predicted image."""
+    lay = InvrImglossLayout()
+    check(lib().invr_imgloss_workspace_layout(H, W, window, C.byref(lay)))
+
+    def view(off, shape, dtype=torch.float32):
+        count = 1
+        for d in shape:
+            count *= d
+        return ws[off:off + count * torch.empty((), dtype=dtype).element_size()].view(dtype).view(*shape)
+    return {'layout': lay, 'rank': view(lay.rank, (H, W), torch.int32), 'img': view(lay.img, (2, 3, H, W)), 'mom': view(lay.mom, (5, 3, H, W)),
+            'smap': view(lay.smap, (3, H, W)), 'pqr': view(lay.pqr, (3, 3, H, W)), 'occ': view(lay.occ, (H, W), torch.uint8),
+            'tvmax': view(lay.tvmax, (2, lay.n_tv)), 'partial': view(lay.partial, (lay.n_partial,), torch.float64),
+            'out8': view(lay.out8, (8,)), 'gimg': view(lay.gimg, (3, H, W))}
 
 
 LPIPS_CIN = (3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512)

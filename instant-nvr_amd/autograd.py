@@ -636,6 +636,89 @@ class TrainLossPerceptualFn(torch.autograd.Function):
         return (g_rgb, None, g_dist, g_terms) + (None,) * 10
 
 
+class _TrainLossTermFn(torch.autograd.Function):
+    """Shared body of TrainLossSsimFn / TrainLossTvFn: TrainLossFn's twin with an image term of include/invr_imgloss.h added to the MSE."""
+    @staticmethod
+    def _common(rgb, gt, dist):
+        """-> the contiguous fp32 inputs, the ray count and the fresh out8 / err tensors of a forward"""
+        rgb, gt = rgb.contiguous(), gt.contiguous().to(torch.float32)
+        n = rgb.shape[0]
+        return rgb, gt, n, torch.empty(8, device=rgb.device), torch.empty(n, device=rgb.device), dist.contiguous() if dist is not None else None
+
+    @classmethod
+    def _guard(cls, ctx):
+        if getattr(ctx.owner, 'gen', None) != ctx.gen:
+            raise RuntimeError('%s.backward: the image-term workspace was handed to a later forward before this backward ran; its '
+                               'intermediates are gone (run backward before the next iteration\'s forward)' % cls.__name__)
+
+
+class TrainLossSsimFn(_TrainLossTermFn):
+    """TrainLossFn's twin for cfg.use_ssim (invr_train_loss_ssim_fwd / _bwd): the regulariser terms and the MSE as there, plus 0.1 (1 -
+    ssim) of the patch re-assembled from mask_at_box (uint8, H*W) under the Gaussian `taps`; every intermediate in the caller's
+    workspace `ws`.  -> (out8 = [loss, img_loss, psnr, reg_dist, offset_loss, pair_loss, ssim_loss, 0], err (n,)); only out8[0]
+    carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, rgb, gt, dist, terms, taps, mask, ws, H, W, w_pair, w_dist, w_off, use_pair, owner=None):
+        rgb, gt, n, out, err, dist_c = _TrainLossTermFn._common(rgb, gt, dist)
+        _abi.check(_abi.lib().invr_train_loss_ssim_fwd(_abi.ptr(rgb), _abi.ptr(gt), _abi.ptr(mask, torch.uint8), _abi.ptr(taps), taps.numel(),
+                                                       _abi.ptr(dist_c), _abi.ptr(terms), n, H, W, w_pair, w_dist, w_off, int(use_pair),
+                                                       _abi.ptr(ws, torch.uint8), ws.numel(), _abi.ptr(out), _abi.ptr(err), _abi.stream_ptr()))
+        ctx.save_for_backward(terms, taps, mask, ws)
+        ctx.has_dist, ctx.n, ctx.args = dist is not None, n, (H, W, w_pair, w_dist, w_off, int(use_pair))
+        ctx.owner, ctx.gen = owner, getattr(owner, 'gen', None)
+        ctx.mark_non_differentiable(err)
+        return out, err
+
+    @staticmethod
+    def backward(ctx, g_out, _g_err):
+        terms, taps, mask, ws = ctx.saved_tensors
+        TrainLossSsimFn._guard(ctx)
+        n = ctx.n
+        g_loss = g_out[:1].contiguous()
+        g_rgb = torch.empty(n, 3, device=terms.device)
+        g_dist = torch.empty(n, device=terms.device) if ctx.has_dist else None
+        g_terms = torch.empty(TERM_LEN, device=terms.device)
+        H, W, w_pair, w_dist, w_off, use_pair = ctx.args
+        _abi.check(_abi.lib().invr_train_loss_ssim_bwd(_abi.ptr(mask, torch.uint8), _abi.ptr(taps), taps.numel(), _abi.ptr(terms), n, H, W,
+                                                       w_pair, w_dist, w_off, use_pair, _abi.ptr(ws, torch.uint8), ws.numel(), _abi.ptr(g_loss),
+                                                       _abi.ptr(g_rgb), _abi.ptr(g_dist), _abi.ptr(g_terms), _abi.stream_ptr()))
+        return (g_rgb, None, g_dist, g_terms) + (None,) * 10
+
+
+class TrainLossTvFn(_TrainLossTermFn):
+    """TrainLossFn's twin for cfg.use_tv_image (invr_train_loss_tv_fwd / _bwd): the regulariser terms and the MSE as there, plus 0.01 tv
+    of the patch re-assembled from mask_at_box with mask_gt from `occ` (uint8 per ray).  -> (out8 = [loss, img_loss, psnr, reg_dist,
+    offset_loss, pair_loss, tv_loss, 0], err (n,)); only out8[0] carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, rgb, gt, dist, terms, occ, mask, ws, H, W, w_pair, w_dist, w_off, use_pair, owner=None):
+        rgb, gt, n, out, err, dist_c = _TrainLossTermFn._common(rgb, gt, dist)
+        _abi.check(_abi.lib().invr_train_loss_tv_fwd(_abi.ptr(rgb), _abi.ptr(gt), _abi.ptr(occ, torch.uint8), _abi.ptr(mask, torch.uint8),
+                                                     _abi.ptr(dist_c), _abi.ptr(terms), n, H, W, w_pair, w_dist, w_off, int(use_pair),
+                                                     _abi.ptr(ws, torch.uint8), ws.numel(), _abi.ptr(out), _abi.ptr(err), _abi.stream_ptr()))
+        ctx.save_for_backward(terms, mask, ws)
+        ctx.has_dist, ctx.n, ctx.args = dist is not None, n, (H, W, w_pair, w_dist, w_off, int(use_pair))
+        ctx.owner, ctx.gen = owner, getattr(owner, 'gen', None)
+        ctx.mark_non_differentiable(err)
+        return out, err
+
+    @staticmethod
+    def backward(ctx, g_out, _g_err):
+        terms, mask, ws = ctx.saved_tensors
+        TrainLossTvFn._guard(ctx)
+        n = ctx.n
+        g_loss = g_out[:1].contiguous()
+        g_rgb = torch.empty(n, 3, device=terms.device)
+        g_dist = torch.empty(n, device=terms.device) if ctx.has_dist else None
+        g_terms = torch.empty(TERM_LEN, device=terms.device)
+        H, W, w_pair, w_dist, w_off, use_pair = ctx.args
+        _abi.check(_abi.lib().invr_train_loss_tv_bwd(_abi.ptr(mask, torch.uint8), _abi.ptr(terms), n, H, W, w_pair, w_dist, w_off, use_pair,
+                                                     _abi.ptr(ws, torch.uint8), ws.numel(), _abi.ptr(g_loss), _abi.ptr(g_rgb), _abi.ptr(g_dist),
+                                                     _abi.ptr(g_terms), _abi.stream_ptr()))
+        return (g_rgb, None, g_dist, g_terms) + (None,) * 10
+
+
 class LazyTrainRet(LazyDict):
     """The train-mode return dict of Renderer.render.  rgb_map / acc_map / raw / occ / reg_distortion_loss and the fused
     regulariser terms (offset_loss, pair_loss: differentiable scalars) are present; the reference's dynamic-shape tensors

@@ -7,14 +7,14 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'libinvr.so')
-SOURCES = ['invr_abi.hip', 'k_cull.hip', 'k_knn.hip', 'k_lists.hip', 'k_warp.hip', 'k_encode.hip', 'k_mlp.hip', 'k_composite.hip', 'k_rays.hip', 'k_prep.hip', 'k_optim.hip', 'k_mlp_bwd.hip', 'k_train.hip', 'k_metrics.hip', 'k_perceptual.hip', 'k_lpips.hip', 'k_mesh.hip', 'k_batch.hip', 'k_sample.hip', 'k_posescene.hip', 'k_surface.hip', 'k_geomaps.hip']
+SOURCES = ['invr_abi.hip', 'k_cull.hip', 'k_knn.hip', 'k_lists.hip', 'k_warp.hip', 'k_encode.hip', 'k_mlp.hip', 'k_composite.hip', 'k_rays.hip', 'k_prep.hip', 'k_optim.hip', 'k_mlp_bwd.hip', 'k_train.hip', 'k_metrics.hip', 'k_perceptual.hip', 'k_imgloss.hip', 'k_lpips.hip', 'k_mesh.hip', 'k_batch.hip', 'k_sample.hip', 'k_posescene.hip', 'k_surface.hip', 'k_geomaps.hip']
 INCLUDE = os.path.join(HERE, '..', 'include')
 
 
 def headers():
     """Every header a source may include: an edit to any of them rebuilds every object."""
     return ([os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith('.h')]
-            + [os.path.join(INCLUDE, h) for h in ('invr.h', 'invr_perceptual.h', 'invr_lpips.h', 'invr_mesh.h', 'invr_batch.h', 'invr_sample.h', 'invr_vertex.h', 'invr_posescene.h', 'invr_surface.h', 'invr_geomaps.h')])
+            + [os.path.join(INCLUDE, h) for h in ('invr.h', 'invr_perceptual.h', 'invr_imgloss.h', 'invr_lpips.h', 'invr_mesh.h', 'invr_batch.h', 'invr_sample.h', 'invr_vertex.h', 'invr_posescene.h', 'invr_surface.h', 'invr_geomaps.h')])
 
 
 # -ffp-contract=off: FMAs only where the source says fmaf(), so the discrete decisions of the path

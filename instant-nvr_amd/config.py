@@ -79,6 +79,8 @@ DEFAULTS = {
     'resd_loss_weight': 0.1,
     'train_fused_loss': True,   # training: NetworkWrapper's objective on the fused node's outputs as one node (autograd.TrainLossFn); False: torch ops
     'fused_perceptual': True,   # training with use_lpips: the perceptual image term on the HIP kernels inside that node (autograd.TrainLossPerceptualFn); False: torch ops
+    'builtin_image_terms': False,   # use_ssim / use_tv_image outside the reference application: True builds invr.losses.SSIM / TVImageLoss; False raises, as before
+    'fused_image_terms': True,   # training with use_ssim / use_tv_image: the term on the HIP kernels inside that node (autograd.TrainLossSsimFn / TrainLossTvFn); False: torch ops
     'train_fused': True,     # training: ONE differentiable node (invr_train_fwd / invr_train_bwd); False: op-by-op autograd graph (autograd.render_train)
     'train_hip_mlp': True,   # training: part MLPs forward + backward on the HIP kernels (False: torch ops, autograd.part_field)
     'voxel_size': [0.005, 0.005, 0.005],   # lib/config/config.py:88: the grid step of the mesh extraction (invr.mesh)

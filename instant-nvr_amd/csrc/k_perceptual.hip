@@ -153,6 +153,14 @@ __global__ void __launch_bounds__(1024) k_perc_assemble(const float* __restrict_
     }
 }
 
+// the one statement of the patch assembly for every image term (k_imgloss.hip launches it too): img_sums[2] = sum |d|, sum d^2
+int launch_patch_assemble(const float* rgb, const float* gt, const uint8_t* mask, int64_t n_rays, int64_t P, int32_t* rank, float* img,
+                          double* img_sums, hipStream_t st) {
+    hipLaunchKernelGGL(k_perc_assemble, dim3(1), dim3(1024), 0, st, rgb, gt, mask, n_rays, P, rank, img, img_sums);
+    INVR_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- the convolution ---------------------------------------------------------------------------------------------------------------
 enum { PC_EP_FWD = 0, PC_EP_FWD_SUM = 1, PC_EP_BWD_MASK = 2, PC_EP_BWD_PLAIN = 3, PC_EP_BWD_IMG = 4 };
 
@@ -480,9 +488,7 @@ static int pc_forward(const float* packed, const float* rgb, const float* gt, co
     const int h = H / 2, w = W / 2;
     const int64_t p = (int64_t)h * w;
     double* partial = pc_at<double>(ws, L.partial);
-    hipLaunchKernelGGL(k_perc_assemble, dim3(1), dim3(1024), 0, st, rgb, gt, mask, n_rays, P, pc_at<int32_t>(ws, L.rank), pc_at<float>(ws, L.img),
-                       partial + L.n_part1 + L.n_part2);
-    INVR_LAUNCH_CHECK();
+    if (launch_patch_assemble(rgb, gt, mask, n_rays, P, pc_at<int32_t>(ws, L.rank), pc_at<float>(ws, L.img), partial + L.n_part1 + L.n_part2, st)) return 1;
     PcConvArgs a = {};
     a.H = H; a.W = W;
     a.in = pc_at<float>(ws, L.img); a.wp = packed + pk.fwd[0]; a.bias = packed + pk.bias[0]; a.out = pc_at<float>(ws, L.a11);

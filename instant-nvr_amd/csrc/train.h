@@ -50,3 +50,6 @@ int launch_train_loss(const float* rgb, const float* gt, const float* dist, cons
                       float w_off, int use_pair, float* out, float* err, hipStream_t st);
 int launch_train_loss_bwd(const float* rgb, const float* gt, const float* terms, int64_t n, float w_pair, float w_dist, float w_off,
                           int use_pair, const float* g_loss, float* g_rgb, float* g_dist, float* g_terms, hipStream_t st);
+// img = zeros; img[mask] = rgb for the predicted and the target patch, planar [2][3][P], and the rank array (k_perceptual.hip: k_perc_assemble)
+int launch_patch_assemble(const float* rgb, const float* gt, const uint8_t* mask, int64_t n_rays, int64_t P, int32_t* rank, float* img,
+                          double* img_sums, hipStream_t st);

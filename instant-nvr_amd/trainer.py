@@ -9,8 +9,11 @@ cfg.use_lpips (True in configs/inb/inb_377.yaml): the patch is re-assembled from
 reference does and handed to a perceptual-loss module — `NetworkWrapper(net, perceptual_loss=...)`, else the host
 application's own `lib.train.trainers.loss.perceptual_loss.PerceptualLoss` when this wrapper runs inside the reference
 (torchvision present), else `invr.losses.PerceptualLoss(weights=cfg.vgg19_weights)`.  With none of the three the
-constructor RAISES: the wrapper never trains a different objective silently.  use_ssim / use_fourier / use_tv_image are
-resolved from the host application the same way (they are off in every INB config) or rejected.
+constructor RAISES: the wrapper never trains a different objective silently.  use_ssim / use_tv_image take the host application's
+`lib.utils.loss_utils.SSIM` / `TVImageLoss` when hosted; outside it the constructor raises as well unless cfg.builtin_image_terms is
+set, which builds `invr.losses.SSIM` / `TVImageLoss` (the same formulas as torch ops); a
+module that is recognisably the reference's runs on the HIP kernels of csrc/k_imgloss.hip inside the objective's one node
+(cfg.fused_image_terms).  use_fourier is resolved from the host application or rejected (it is off in every INB config).
 """
 import numpy as np
 import torch
@@ -53,6 +56,14 @@ def assemble_patch(values, mask_at_box, H, W):
     return img.reshape(H, W, v.shape[-1])
 
 
+def _as_bytes(t, device):
+    """A mask as the kernels read it: one byte per element, non-zero = set, flat, on `device` — a view where it already is that."""
+    t = t.reshape(-1).to(device)
+    if t.dtype == torch.bool:
+        return t.contiguous().view(torch.uint8)
+    return (t if t.dtype == torch.uint8 else t.ne(0).view(torch.uint8)).contiguous()
+
+
 class NetworkWrapper(nn.Module):
     def __init__(self, net, perceptual_loss=None):
         super().__init__()
@@ -87,24 +98,36 @@ class NetworkWrapper(nn.Module):
                                      ('use_tv_image', 'lib.train.trainers.loss.tv_image_loss', 'TVImageLoss', 'tv_image_loss')):
             if cfg.get(flag, False):                                                     # :31-38, off in every INB config
                 host = _host_loss(mod, cls)
+                if host is None and flag != 'use_fourier' and cfg.get('builtin_image_terms', False):
+                    from . import losses
+                    host = getattr(losses, cls)                                           # the same formula as torch ops
                 if host is None:
-                    raise RuntimeError('cfg.%s is set but %s.%s is only available inside the reference application' % (flag, mod, cls))
+                    raise RuntimeError('cfg.%s is set but %s.%s is only available inside the reference application%s'
+                                       % (flag, mod, cls, '' if flag == 'use_fourier' else
+                                          '; set cfg.builtin_image_terms True to build invr.losses.%s instead' % cls))
                 setattr(self, attr, host(window_size=11) if flag == 'use_ssim' else host())
 
     def _fused_objective(self, ret, batch):
         """split 'train' on the fused node: the whole objective as ONE autograd node, same terms, same order of additions as the
         op-by-op form below -> (loss, scalar_stats) or None when it does not apply.  The image term is the plain MSE
         (autograd.TrainLossFn) or, with cfg.use_lpips and a perceptual-loss module that is recognisably the reference's VGG19 prefix
-        (losses.vgg_convs), the perceptual loss on the HIP kernels (autograd.TrainLossPerceptualFn); any other module — an injected
-        stand-in — keeps the op-by-op path."""
+        (losses.vgg_convs), the perceptual loss on the HIP kernels (autograd.TrainLossPerceptualFn); with cfg.use_ssim / use_tv_image
+        and a module that is recognisably the reference's, the MSE plus that term (autograd.TrainLossSsimFn / TrainLossTvFn).  Any
+        other module — an injected stand-in — and use_fourier keep the op-by-op path.  The reference's precedence holds: use_lpips,
+        use_ssim, use_fourier, use_tv_image."""
         cfg = self.cfg
         last = getattr(self.renderer, 'last_train', None)
-        if (last is None or last.get('terms') is None or not cfg.get('train_fused_loss', True)
-                or cfg.get('use_ssim', False) or cfg.get('use_fourier', False) or cfg.get('use_tv_image', False)):
+        if last is None or last.get('terms') is None or not cfg.get('train_fused_loss', True):
             return None
         dist = ret['reg_distortion_loss'][0] if dict.__contains__(ret, 'reg_distortion_loss') else None
         if cfg.get('use_lpips', False):
             return self._fused_perceptual_objective(ret, batch, last, dist)
+        if cfg.get('use_ssim', False):
+            return self._fused_image_term_objective(ret, batch, last, dist, 'ssim')
+        if cfg.get('use_fourier', False):
+            return None
+        if cfg.get('use_tv_image', False):
+            return self._fused_image_term_objective(ret, batch, last, dist, 'tv')
         from .autograd import TrainLossFn
         out, err = TrainLossFn.apply(ret['rgb_map'][0], batch['rgb'][0], dist, last['terms'], float(cfg.pair_loss_weight), float(cfg.reg_dist_weight),
                                      float(cfg.resd_loss_weight), bool(cfg.use_pair_reg))
@@ -136,6 +159,61 @@ class NetworkWrapper(nn.Module):
                                                bool(cfg.use_pair_reg), fp)
         stats = {'loss': out[0], 'img_loss': out[1].detach(), 'psnr': out[2:3].detach(), 'offset_loss': out[4].detach(),
                  'lpips_loss': out[6].detach()}
+        if dist is not None:
+            stats['reg_dist'] = out[3].detach()
+        if cfg.use_pair_reg:
+            stats['pair_loss'] = out[5].detach()
+        ret['error'] = err[None]
+        return out[0], stats
+
+    def _recognised_ssim_window(self):
+        """losses.ssim_window_size of self.ssim_loss, looked at again only when the module or its window was replaced or written to
+        (the rule compares the window's values: not a per-iteration cost)"""
+        mod = getattr(self, 'ssim_loss', None)
+        win = getattr(mod, 'window', None)
+        seen = getattr(self, '_ssim_seen', None)
+        state = (getattr(mod, 'window_size', None), getattr(mod, 'size_average', None), getattr(win, '_version', None))
+        if seen is None or seen[0] is not mod or seen[1] is not win or seen[2] != state:
+            from . import losses
+            self._ssim_seen = (mod, win, state, losses.ssim_window_size(mod))
+        return self._ssim_seen[3]
+
+    def _fused_image_term_objective(self, ret, batch, last, dist, term):
+        """term 'ssim' | 'tv' on the HIP kernels (include/invr_imgloss.h) -> (loss, scalar_stats), or None where the op-by-op path has to
+        run: cfg.fused_image_terms off, tensors that are not fp32 on one device, a side outside [2, 2048], a module no rule recognises."""
+        cfg = self.cfg
+        from . import losses
+        if not cfg.get('fused_image_terms', True):
+            return None
+        rgb, gt = ret['rgb_map'][0], batch['rgb'][0]
+        if rgb.dtype != torch.float32 or gt.dtype != torch.float32 or gt.device != rgb.device or last['terms'].device != rgb.device:
+            return None
+        H, W = int(batch['H'].item()), int(batch['W'].item())                           # as the reference reads them (:188-189)
+        if min(H, W) < 2 or max(H, W) > losses.IMGLOSS_MAX_SIDE:
+            return None
+        if term == 'ssim':
+            window = self._recognised_ssim_window()
+            if window is None:
+                return None
+        else:
+            window = 1
+            if not losses.is_tv_module(getattr(self, 'tv_image_loss', None), _host_loss('lib.train.trainers.loss.tv_image_loss', 'TVImageLoss')):
+                return None
+        if not hasattr(self, '_fused_image_terms'):
+            self._fused_image_terms = losses.FusedImageTerms()
+        ft = self._fused_image_terms
+        mask = _as_bytes(batch['mask_at_box'][0], rgb.device)
+        w = (float(cfg.pair_loss_weight), float(cfg.reg_dist_weight), float(cfg.resd_loss_weight), bool(cfg.use_pair_reg))
+        if term == 'ssim':
+            from .autograd import TrainLossSsimFn
+            out, err = TrainLossSsimFn.apply(rgb, gt, dist, last['terms'], ft.taps(window, rgb.device), mask, ft.workspace(H, W, window, rgb.device),
+                                             H, W, *w, ft)
+        else:
+            from .autograd import TrainLossTvFn
+            occ = _as_bytes(batch['occupancy'], rgb.device)                                # occ_gt.bool() (:207): any non-zero byte is set
+            out, err = TrainLossTvFn.apply(rgb, gt, dist, last['terms'], occ, mask, ft.workspace(H, W, window, rgb.device), H, W, *w, ft)
+        stats = {'loss': out[0], 'img_loss': out[1].detach(), 'psnr': out[2:3].detach(), 'offset_loss': out[4].detach(),
+                 term + '_loss': out[6].detach()}
         if dist is not None:
             stats['reg_dist'] = out[3].detach()
         if cfg.use_pair_reg:

@@ -4,7 +4,10 @@ Reports the un-synchronised iteration time (the loop only syncs at the end) and 
   python tools/train_bench.py --lpips [--iters 50]
 The same iteration with cfg.use_lpips True (the configs/inb/inb_377.yaml default) and a seeded PerceptualLoss(allow_random=True) at a
 64 x 64 and a 56 x 56 patch: cfg.fused_perceptual False (torch ops) against True (csrc/k_perceptual.hip), interleaved in one process,
-then the per-launch device times of the perceptual kernels (profiles/perceptual_loss.md)."""
+then the per-launch device times of the perceptual kernels (profiles/perceptual_loss.md).
+  python tools/train_bench.py --ssim | --tv [--iters 50]
+The same iteration with cfg.use_ssim / cfg.use_tv_image True at a 64 x 64 patch: the plain-MSE iteration, cfg.fused_image_terms False
+(torch ops) and True (csrc/k_imgloss.hip), interleaved in one process, then the launches per iteration (profiles/image_terms.md)."""
 import argparse
 import os
 import sys
@@ -29,6 +32,8 @@ ap.add_argument('--torch-adam', action='store_true')
 ap.add_argument('--prof', action='store_true')
 ap.add_argument('--thresh', type=float, default=0.05)
 ap.add_argument('--lpips', action='store_true', help='A/B of the use_lpips iteration: cfg.fused_perceptual False against True')
+ap.add_argument('--ssim', action='store_true', help='A/B of the use_ssim iteration: cfg.fused_image_terms False against True, next to plain MSE')
+ap.add_argument('--tv', action='store_true', help='the same for use_tv_image')
 args = ap.parse_args()
 DEV = 'cuda:0'
 cfg = make_cfg(N_samples=args.samples, smpl_thresh=args.thresh)
@@ -95,8 +100,60 @@ def lpips_ab():
                         print('    %-90s x%d per iteration  %.1f us each' % (e.key[:90], e.count // 5, e.device_time_total / e.count))
 
 
+def image_term_ab(flag):
+    torch.manual_seed(0)
+    setattr(net.cfg, flag, True)
+    net.cfg.builtin_image_terms = True
+    wrap = NetworkWrapper(net)                              # builds invr.losses.SSIM / TVImageLoss
+    opt = driver.make_optimizer(net, fused=not args.torch_adam)
+    gb = patch(64)
+    gb['H'], gb['W'] = gb['H'].cpu(), gb['W'].cpu()          # as TrainSet hands them: host tensors, no read-back per iteration
+    arms = (('mse', False, True), ('torch ops', True, False), ('fused', True, True))
+    ms = {a[0]: [] for a in arms}
+    it = 0
+    for rep in range(3):                                   # interleaved: drift of the box shows as spread within an arm
+        for name, on, fused in arms:
+            setattr(net.cfg, flag, on)
+            net.cfg.fused_image_terms = fused
+            for _ in range(5):
+                it += 1
+                gb['iter_step'] = it + 1
+                loss = driver.train_step(wrap, opt, gb, it + 1)[0]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.iters):
+                it += 1
+                gb['iter_step'] = it + 1
+                loss = driver.train_step(wrap, opt, gb, it + 1)[0]
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) / args.iters * 1e3)
+    print('%s 64x64 patch, %d rays x %d samples, ms per iteration: %s   last loss %.5f'
+          % (flag, gb['ray_o'].shape[1], args.samples,
+             '   '.join('%s %s (median %.3f)' % (k, np.round(v, 3).tolist(), np.median(v)) for k, v in ms.items()), float(loss)))
+    from torch.profiler import profile, ProfilerActivity
+    for name, on, fused in arms:
+        setattr(net.cfg, flag, on)
+        net.cfg.fused_image_terms = fused
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(5):
+                it += 1
+                gb['iter_step'] = it + 1
+                driver.train_step(wrap, opt, gb, it + 1)
+            torch.cuda.synchronize()
+        ev = [e for e in prof.key_averages() if e.device_time_total > 0]
+        print('  %-9s: %d device launches per iteration, %.1f us of device time per iteration'
+              % (name, sum(e.count for e in ev) // 5, sum(e.device_time_total for e in ev) / 5))
+        if fused and on:
+            for e in sorted(ev, key=lambda e: -e.device_time_total):
+                if any(k in e.key for k in ('k_ssim', 'k_tv', 'k_imgloss', 'k_train_loss_term', 'k_perc_assemble')):
+                    print('    %-90s x%d per iteration  %.1f us each' % (e.key[:90], e.count // 5, e.device_time_total / e.count))
+
+
 if args.lpips:
     lpips_ab()
+    sys.exit(0)
+if args.ssim or args.tv:
+    image_term_ab('use_ssim' if args.ssim else 'use_tv_image')
     sys.exit(0)
 s = args.rays_side
 gb = patch(s)
